@@ -18,7 +18,12 @@ Multi-GPU: one process per GPU; the headline is replicas (every rank its own TT 
 data-path collective). The "cfg5" object adds BASELINE configs[4]: order-16 rank-512 round() sharded
 over all ranks by mode slices (xerus_amd.dist; one r x r all-reduce per edge over RCCL), strong scaling.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu] [--no-cfg5]
+A plain run (no --full) sets up, warms up, times the K steps, writes --dump-outputs and prints the headline
+line: metric / value / ms_per_step and the workload's config. Everything else above and below (phase split,
+fp32 <x,y>, roofline passes, CPU baseline, cfg5, the per-config extras) runs only with --full, after the timed
+steps, and adds its keys to the same line.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-cpu] [--no-cfg5] [--no-extras]]
 """
 import argparse
 import json
@@ -35,6 +40,7 @@ FP64_MFMA_PEAK_TFLOPS = 78.6   # gfx950 dense fp64 matrix peak (MI355X spec)
 FP32_MFMA_PEAK_TFLOPS = 157.3  # gfx950 dense fp32 matrix peak (v_mfma_f32_*_f32, MI355X_MICROARCH.md)
 HBM_PEAK_GBS = 8000.0           # HBM3E spec peak (MI355X_MICROARCH.md; 6.29 TB/s measured for a float4 copy)
 SEED = 0xBAADF00D               # src/xerus/test/test.cpp:105
+DUMP_MAX_BYTES = 60 * 10 ** 6   # --dump-outputs budget for all files together (under 64 MB with the .npy headers)
 
 
 def tt_ranks(d, n, r):
@@ -75,6 +81,19 @@ def random_cores(xe, dims, ranks, seed):
     xe.seed(seed)
     tt = xe.TTTensor.random_raw(list(dims), list(ranks[1:-1]))
     return [np.ascontiguousarray(tt.get_component(k).to_ndarray()) for k in range(len(dims))]
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array of the dict as path/<name>.npy in float64. An array larger than its share of
+    DUMP_MAX_BYTES is written as a fixed sample instead: its row-major entries at the sorted indices that
+    default_rng(SEED) draws without replacement (the same indices for the same shape in every run and build)."""
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_MAX_BYTES // 8 // len(arrays)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.size > cap:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(SEED).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def load_traffic():
@@ -490,6 +509,12 @@ def main():
     ap.add_argument("--order", type=int, default=10)
     ap.add_argument("--mode", type=int, default=20)
     ap.add_argument("--rank", type=int, default=256)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (the value of <x,y>, the ranks and the "
+                         "cores of the rounded x) as DIR/<name>.npy (float64; large cores as a fixed seeded sample)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the diagnostics: phase split, fp32 <x,y>, roofline passes, CPU "
+                         "baseline, cfg5 and the per-config lines (the --no-* options below trim them)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--no-overlap", action="store_true",
                     help="sequential step (<x,y> waited for before the round starts) instead of the async inner product")
@@ -540,7 +565,7 @@ def main():
 
     def step_seq(timing=None):
         t0 = time.perf_counter()
-        x.dot(y)
+        xy = x.dot(y)
         t1 = time.perf_counter()
         x.round(r)
         h.synchronize()
@@ -548,19 +573,22 @@ def main():
         if timing is not None:
             timing["dot"] += t1 - t0
             timing["round"] += t2 - t1
+        return xy
 
     def step_overlap(timing=None):
         # <x,y> on the handle's side streams (xrs_tt_dot_async) beside x.round(r) on the main stream; the
         # round's release of x's old cores waits for the inner product (stream-ordered fence)
         fut = x.dot_async(y)
         x.round(r)
-        fut.result()
+        xy = fut.result()
         h.synchronize()
+        return xy
 
     step = step_seq if args.no_overlap else step_overlap
 
+    xy = None
     for _ in range(args.warmup):
-        step()
+        xy = step()
 
     def barrier():
         h.synchronize()
@@ -572,9 +600,56 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        xy = step()
     barrier()
     elapsed = time.perf_counter() - t0
+    if dist is not None:
+        t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    ms_step = elapsed / args.steps * 1e3
+    value = world * f_step * args.steps / elapsed / 1e9
+    assert x.r == ranks
+
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed back: the value of <x,y> and x as round() left it (ranks + cores)
+        arrays = {"dot": np.array([xy]), "ranks": np.array(x.r, dtype=np.float64)}
+        arrays.update({f"core_{k:02d}": c for k, c in enumerate(x.cores())})
+        dump_outputs(args.dump_outputs, arrays)
+
+    out = {
+        "metric": "GFLOP/s on TT contraction + TT-round sweep time, order-10 rank-256",
+        "value": round(value, 3),
+        "unit": "GFLOP/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_step, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (TTTensor::random semantics: N(0,1) cores from the product's libstdc++ mt19937_64 "
+                "seeded 0xBAADF00D + 2 rank (+1 for y), move_core(0) on the GPU)",
+        "config": {
+            "workload": f"TT order-{d} n={n} rank-{r}: <x,y> + x.round({r}) per step",
+            "order": d, "mode_size": n, "rank": r, "ranks": ranks,
+            "step": ("sequential: x.dot(y), then x.round" if args.no_overlap else
+                     "overlapped: x.dot_async(y) on side streams beside x.round on the main stream, both waited for"),
+            "gflop_per_step": round(f_step / 1e9, 4),
+            "parallelism": f"replicas x{world}",
+        },
+    }
+    if not args.full:
+        # plain run: the headline line only
+        x.free()
+        y.free()
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
     # phase split (diagnostic, not the headline): the same steps run sequentially, host-timed per call
     timing = {"dot": 0.0, "round": 0.0}
     for _ in range(args.steps):
@@ -625,14 +700,6 @@ def main():
     prof_ov, elapsed_ev_ov = events_pass(step) if step is not step_seq else (prof, elapsed_ev)
     # the separate split-K reduce launches that complete some of those GEMMs (k_splitk_reduce*), same steps
     prof_red, _ = events_pass(step_seq, capi.KFAM_SPLITK)
-
-    if dist is not None:
-        t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
-
-    ms_step = elapsed / args.steps * 1e3
-    value = world * f_step * args.steps / elapsed / 1e9
     assert x.r == ranks
 
     cfg5 = None
@@ -750,36 +817,13 @@ def main():
                 "cpu_model": host["model"],
                 "threads_rule": host["rule"],
             }
-        out = {
-            "metric": "GFLOP/s on TT contraction + TT-round sweep time, order-10 rank-256",
-            "value": round(value, 3),
-            "unit": "GFLOP/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_step, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic (TTTensor::random semantics: N(0,1) cores from the product's libstdc++ mt19937_64 "
-                    "seeded 0xBAADF00D + 2 rank (+1 for y), move_core(0) on the GPU)",
-            "config": {
-                "workload": f"TT order-{d} n={n} rank-{r}: <x,y> + x.round({r}) per step",
-                "order": d, "mode_size": n, "rank": r, "ranks": ranks,
-                "step": ("sequential: x.dot(y), then x.round" if args.no_overlap else
-                         "overlapped: x.dot_async(y) on side streams beside x.round on the main stream, both waited for"),
-                "dot_ms": round(timing["dot"] / args.steps * 1e3, 4),
-                "dot_f32": dot_f32,
-                "round_sweep_ms": round(timing["round"] / args.steps * 1e3, 4),
-                "sequential_ms_per_step": round((timing["dot"] + timing["round"]) / args.steps * 1e3, 4),
-                "gflop_per_step": round(f_step / 1e9, 4),
-                "parallelism": f"replicas x{world}",
-            },
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-            "cfg5": cfg5,
-        }
+        out["config"].update({
+            "dot_ms": round(timing["dot"] / args.steps * 1e3, 4),
+            "dot_f32": dot_f32,
+            "round_sweep_ms": round(timing["round"] / args.steps * 1e3, 4),
+            "sequential_ms_per_step": round((timing["dot"] + timing["round"]) / args.steps * 1e3, 4),
+        })
+        out.update({"roofline": roofline, "cpu_baseline": cpu, "cfg5": cfg5})
         out.update(extras)
         print(json.dumps(out), flush=True)
     if dist is not None:

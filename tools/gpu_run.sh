@@ -7,13 +7,13 @@
 #   tests             the whole -m gpu suite                      -> tests.log
 #   test:PATH         one test file / node id (-m gpu)            -> test_<n>.log
 #   smoke             __graft_entry__.smoke()                     -> smoke.log
-#   bench             python bench.py (default line)             -> bench.json
-#   benchq            bench.py --no-cpu (no CPU leg)              -> benchq.json
+#   bench             python bench.py --full (every key)         -> bench.json
+#   benchq            bench.py --full --no-cpu (no CPU leg)       -> benchq.json
 #   trace             rocprofv3 --kernel-trace --stats of the step-only SEQUENTIAL bench
-#                     (bench.py --no-cpu --no-cfg5 --no-extras --no-overlap: the roofline pass's step)
+#                     (bench.py --full --no-cpu --no-cfg5 --no-extras --no-overlap: the roofline pass's step)
 #                                                                 -> trace/   (+ roofline.txt)
 #   traceov           the same for the headline (overlapped) step -> traceov/
-#   tracefull         rocprofv3 of the whole default bench (--no-cpu) -> tracefull/
+#   tracefull         rocprofv3 of the whole bench (--full --no-cpu) -> tracefull/
 #   pmc               FETCH_SIZE / WRITE_SIZE calibration + PMC passes over the step-only bench -> pmc/
 #   py:SCRIPT[,ARG..] python -u SCRIPT ARG..                       -> py_<n>.txt
 #   prof:SCRIPT[,ARG..] rocprofv3 --kernel-trace --stats of python3 SCRIPT ARG.. -> prof_<n>/
@@ -24,7 +24,7 @@ shift
 D=gpurun_out/$TAG
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p "$D"
-STEPCMD="python3 bench.py --no-cpu --no-cfg5 --no-extras --no-overlap --steps 20 --warmup 3"
+STEPCMD="python3 bench.py --full --no-cpu --no-cfg5 --no-extras --no-overlap --steps 20 --warmup 3"
 n=0
 for step in "$@"; do
   n=$((n + 1))
@@ -40,20 +40,20 @@ for step in "$@"; do
       timeout -k 10 180 python -u -c "import __graft_entry__ as g; g.smoke()" > "$D/smoke.log" 2>&1
       rc=$?; tail -2 "$D/smoke.log" ;;
     bench)
-      timeout -k 10 400 python bench.py > "$D/bench.json" 2> "$D/bench.err"
+      timeout -k 10 400 python bench.py --full > "$D/bench.json" 2> "$D/bench.err"
       rc=$?; cut -c1-600 "$D/bench.json" ;;
     benchq)
-      timeout -k 10 300 python bench.py --no-cpu > "$D/benchq.json" 2> "$D/benchq.err"
+      timeout -k 10 300 python bench.py --full --no-cpu > "$D/benchq.json" 2> "$D/benchq.err"
       rc=$?; cut -c1-600 "$D/benchq.json" ;;
     trace)
       timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$D/trace" -o step --output-format csv -- $STEPCMD > "$D/trace.json" 2> "$D/trace.err" \
         && python3 tools/roofline_from_trace.py "$D/trace" "$D/trace.json" > "$D/roofline.txt"
       rc=$?; cat "$D/roofline.txt" 2>/dev/null | tail -12 ;;
     traceov)
-      timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$D/traceov" -o step --output-format csv -- python3 bench.py --no-cpu --no-cfg5 --no-extras --steps 20 --warmup 3 > "$D/traceov.json" 2> "$D/traceov.err"
+      timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$D/traceov" -o step --output-format csv -- python3 bench.py --full --no-cpu --no-cfg5 --no-extras --steps 20 --warmup 3 > "$D/traceov.json" 2> "$D/traceov.err"
       rc=$? ;;
     tracefull)
-      timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$D/tracefull" -o bench --output-format csv -- python3 bench.py --no-cpu > "$D/tracefull.json" 2> "$D/tracefull.err"
+      timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$D/tracefull" -o bench --output-format csv -- python3 bench.py --full --no-cpu > "$D/tracefull.json" 2> "$D/tracefull.err"
       rc=$? ;;
     pmc)
       /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 tools/fetch_calib.hip -o "$D/fetch_calib" \

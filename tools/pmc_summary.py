@@ -70,7 +70,7 @@ if "FETCH_SIZE" in g and "WRITE_SIZE" in g:
         "calibration": {"fetch_factor": ff, "write_factor": wf, "measured": cal.get("factors", {})},
         "dispatches": g["FETCH_SIZE"]["dispatches"],
         "source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over " + os.environ.get(
-                      "PMC_CMD", "python3 bench.py --no-cpu --no-cfg5 --no-extras --no-overlap --steps 20 --warmup 3 (tools/gpu_run.sh pmc)") +
+                      "PMC_CMD", "python3 bench.py --full --no-cpu --no-cfg5 --no-extras --no-overlap --steps 20 --warmup 3 (tools/gpu_run.sh pmc)") +
                   ", mean per GEMM dispatch (k_gemm_glds + k_gemm_f64), corrected by the 8-B load/store calibration of "
                   "tools/fetch_calib.hip (FETCH x%.3f, WRITE x%.3f); %s/pmc_summary.json" % (ff, wf, dst),
     }

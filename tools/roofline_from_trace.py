@@ -1,5 +1,5 @@
 """Recompute bench.py's roofline.frac from a rocprofv3 kernel trace of the step-only SEQUENTIAL bench
-(tools/gpu_run.sh step `trace`: bench.py --no-cpu --no-cfg5 --no-extras --no-overlap).
+(tools/gpu_run.sh step `trace`: bench.py --full --no-cpu --no-cfg5 --no-extras --no-overlap).
 
 The bench runs W warm-up steps, K timed steps, K phase-split steps, the fp32 / fp64 side dots, K steps of the
 GEMM HIP-event pass and (r06) K steps of the split-K-reduce event pass, all the same sequential step (<x,y>
