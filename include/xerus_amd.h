@@ -240,6 +240,34 @@ int xrs_tt_dot_f32(xrs_handle_t handle, double* result, size_t d, const size_t* 
                    const size_t* rx, const double* const* xcores,
                    const size_t* ry, const double* const* ycores);
 
+/* ---------------------------------------------------------------- Riemannian TT (algorithms/retractions.cpp) */
+/** Projection of the TT Z (ranks rz, any gauge) onto the tangent space of the fixed-rank manifold at the TT U
+ *  (ranks ru, right-orthogonal with the core at 0), the constructor TTTangentVector(base, direction)
+ *  (retractions.cpp:82-130): with UV_{k+1} = sum_i U_k[:,i,:]^T UV_k Z_k[:,i,:], UU_{k+1} the same with U in
+ *  both places and R_k the right environment of U against Z (:121),
+ *      V_k = UU_k^+ UV_k Z_k R_k^T,   V_k -= (V_k U_k^T) U_k for k >= 1 (over the (n, r_{k+1}) unfolding).
+ *  V[k] (ru[k], n[k], ru[k+1]) and the left Grams UU[k] (ru[k] x ru[k], UU[0] = 1) are new buffers of the
+ *  handle's pool (release with xrs_free). The d - 1 systems are solved by one batched Cholesky launch with a
+ *  device-side certificate (no squared pivot <= EPSILON max diag UU_k); an uncertified edge uses the SVD
+ *  pseudo-inverse with the reference's cut (singular values <= EPSILON sigma_max dropped, tensor.cpp:1568-1574).
+ *  *fallback_edges (host, may be NULL): the number of such edges. The two left chains and the right chain run
+ *  on three streams; the certificate words are the only data read back. ru[k] <= 512. Synchronises. */
+int xrs_tt_tangent_project(xrs_handle_t handle, size_t d, const size_t* n, const size_t* ru, const double* const* U,
+                           const size_t* rz, const double* const* Z, double** V, double** UU, size_t* fallback_edges);
+/** The rank-2r TT of the tangent vector with components V at the base U (both with ranks r), or of base +
+ *  tangent vector with add_base (TTTangentVector::operator TTTensor / added_to_base, retractions.cpp:186-260):
+ *  first core [U_0 | V_0] (or [U_0 | U_0 + V_0]), interior cores [[U_k, V_k], [0, U_k]], last core [V_k ; U_k];
+ *  d = 1: V_0 (or V_0 + U_0). One HBM-bound launch writes every core (16-byte accesses where r[k+1] is even)
+ *  into new buffers of the handle's pool, out[k]: (k ? 2 r[k] : 1, n[k], k + 1 < d ? 2 r[k+1] : 1). Bit-exact.
+ *  No canonicalisation (the reference then calls move_core(0)). Enqueued only. */
+int xrs_tt_tangent_to_tt(xrs_handle_t handle, size_t d, const size_t* n, const size_t* r, const double* const* U,
+                         const double* const* V, int add_base, double** out);
+/** Inner product sum_k <UU[k] A_k, B_k> of two tangent vectors at the same base (TTTangentVector::scalar_product,
+ *  retractions.cpp:167-179) with the Grams UU of xrs_tt_tangent_project: batched products, one reduction
+ *  launch over all components, one device-to-host copy. *result on host. Synchronises. */
+int xrs_tt_tangent_dot(xrs_handle_t handle, double* result, size_t d, const size_t* n, const size_t* r,
+                       const double* const* UU, const double* const* A, const double* const* B);
+
 /** All-reduce (element-wise sum over all ranks) of `count` doubles at the device pointer `buf`, in place.
  *  Called by the sharded TT entry points with the handle's stream synchronised; returns 0 on success.
  *  The Python layer (xerus_amd.dist) binds it to torch.distributed (RCCL over xGMI on MI355X).

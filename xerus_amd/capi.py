@@ -76,6 +76,12 @@ SIGNATURES = {
                                           C.c_double, C.c_int, C.c_int, _DP, _DP, C.POINTER(C.c_int)]),
     "xrs_tt_dot_sharded": (C.c_int, [_DP, C.POINTER(C.c_double), _SZ, C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(_DP),
                                      C.POINTER(_SZ), C.POINTER(_DP), _DP, _DP]),
+    "xrs_tt_tangent_project": (C.c_int, [_DP, _SZ, C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(_DP), C.POINTER(_SZ),
+                                         C.POINTER(_DP), C.POINTER(_DP), C.POINTER(_DP), C.POINTER(_SZ)]),
+    "xrs_tt_tangent_to_tt": (C.c_int, [_DP, _SZ, C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(_DP), C.POINTER(_DP), C.c_int,
+                                       C.POINTER(_DP)]),
+    "xrs_tt_tangent_dot": (C.c_int, [_DP, C.POINTER(C.c_double), _SZ, C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(_DP),
+                                     C.POINTER(_DP), C.POINTER(_DP)]),
     "xrs_tt_last_round_path": (C.c_int, [_DP]),
     "xrs_tt_soft_threshold": (C.c_int, [_DP, _SZ, C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(_DP), C.c_int, _SZ,
                                         C.POINTER(C.c_double)]),
@@ -206,6 +212,22 @@ class Handle:
         tab = lambda xs: (_DP * max(1, cnt))(*[_DP(x.ptr) for x in xs])  # noqa: E731
         _check("xrs_gemm_batched", self.lib.xrs_gemm_batched(self.h, cnt, tab(Cs), M, N, alpha, tab(As), lda, int(transA),
                                                             K, tab(Bs), ldb, int(transB)))
+
+    def tangent_to_tt(self, n, r, Us, Vs, add_base: bool):
+        """xrs_tt_tangent_to_tt: the rank-2r block cores of a tangent vector (components Vs at the base Us, both
+        lists of DeviceArrays with ranks r = [1, .., 1]) as new DeviceArrays."""
+        d = len(n)
+        tab = lambda xs: (_DP * d)(*[_DP(x.ptr) for x in xs])  # noqa: E731
+        out = (_DP * d)()
+        _check("xrs_tt_tangent_to_tt", self.lib.xrs_tt_tangent_to_tt(self.h, d, _arr(n), _arr(r), tab(Us), tab(Vs),
+                                                                    int(add_base), out))
+        cores = []
+        for k in range(d):
+            shape = (2 * r[k] if k else 1, n[k], 2 * r[k + 1] if k + 1 < d else 1)
+            c = DeviceArray(self, shape, ptr=out[k])
+            c.owned = True
+            cores.append(c)
+        return cores
 
     def matmul(self, A: "DeviceArray", transA: bool, B: "DeviceArray", transB: bool, alpha: float = 1.0):
         """Row-major C = alpha*op(A)*op(B) with the reference's inline-overload ld convention."""

@@ -11,8 +11,10 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <cstdint>
 #include <cstring>
 
+#include "xerus_amd.h"
 #include "xerus.h"
 
 namespace py = pybind11;
@@ -57,6 +59,10 @@ PYBIND11_MODULE(xerus, m) {
     m.attr("EPSILON") = EPSILON;
     m.def("set_device", &gpu::set_device);
     m.def("synchronize", &gpu::synchronize);
+    m.def("stream", [] { return reinterpret_cast<std::uintptr_t>(xrs_get_stream(gpu::handle())); },
+          "the hipStream_t of the calling thread's handle as an integer (for timing with HIP events)");
+    m.def("last_round_path", [] { return xrs_tt_last_round_path(gpu::handle()); },
+          "algorithm of the calling thread's last TT round: 1 chain, 2 certified truncation, 3 reference sweeps, 4 general");
     m.def("seed", [](uint64 _s) {
         misc::randomEngine.seed(_s);
         misc::defaultNormalDistribution.reset();
@@ -383,6 +389,123 @@ PYBIND11_MODULE(xerus, m) {
     m.attr("DMRG_SPD") = py::cast(ALSVariant(DMRG_SPD));
     m.attr("ASD") = py::cast(ALSVariant(ASD));
     m.attr("ASD_SPD") = py::cast(ALSVariant(ASD_SPD));
+
+    // ------------------------------------------------------------------ Riemannian optimisation
+    // (algorithms/retractions.h, steepestDescent.h, cg.h)
+    py::class_<TTTangentVector>(m, "TTTangentVector")
+        .def(py::init<>())
+        .def(py::init<const TTTangentVector&>())
+        .def(py::init<const TTTensor&, const TTTensor&>(), py::arg("base"), py::arg("direction"))
+        .def_readonly("baseL", &TTTangentVector::baseL)
+        .def_readwrite("components", &TTTangentVector::components)
+        .def_readonly("fallbackEdges", &TTTangentVector::fallbackEdges)
+        .def("set_base", &TTTangentVector::set_base)
+        .def("scalar_product", &TTTangentVector::scalar_product)
+        .def("frob_norm", &TTTangentVector::frob_norm)
+        .def("to_tt", [](const TTTangentVector& _v) { return TTTensor(_v); })
+        .def("added_to_base", &TTTangentVector::added_to_base)
+        .def(py::self += py::self)
+        .def(py::self -= py::self)
+        .def(py::self *= value_t())
+        .def(py::self * value_t())
+        .def(value_t() * py::self)
+        .def("__copy__", [](const TTTangentVector& _v) { return TTTangentVector(_v); });
+
+    py::class_<HOSVDRetraction>(m, "HOSVDRetraction")
+        .def(py::init<size_t>())
+        .def(py::init<const std::vector<size_t>&>())
+        .def_readonly("roundByVector", &HOSVDRetraction::roundByVector)
+        .def_readonly("rank", &HOSVDRetraction::rank)
+        .def_readonly("rankVector", &HOSVDRetraction::rankVector)
+        .def("__call__", [](const HOSVDRetraction& _r, TTTensor& _U, const TTTensor& _change) { _r(_U, _change); })
+        .def("__call__", [](const HOSVDRetraction& _r, TTTensor& _U, const TTTangentVector& _change) { _r(_U, _change); });
+    m.def("HOSVDRetractionI", &HOSVDRetractionI);
+    m.def("HOSVDRetractionII", &HOSVDRetractionII);
+    m.def("ALSRetractionI", &ALSRetractionI);
+    m.def("ALSRetractionII", &ALSRetractionII);
+    m.def("SubmanifoldRetractionI", &SubmanifoldRetractionI);
+    m.def("SubmanifoldRetractionII", &SubmanifoldRetractionII);
+    m.def("ProjectiveVectorTransport", &ProjectiveVectorTransport);
+
+    // A retraction or transport given from Python (a bound one or any callable) updates its first / second
+    // argument in place, so the arguments go to Python as references to the solver's objects, not copies.
+    auto retractionII = [](py::object _f) -> TTRetractionII {
+        return [_f](TTTensor& _U, const TTTensor& _change) {
+            _f(py::cast(&_U, py::return_value_policy::reference), py::cast(&_change, py::return_value_policy::reference));
+        };
+    };
+    auto retractionI = [](py::object _f) -> TTRetractionI {
+        return [_f](TTTensor& _U, const TTTangentVector& _change) {
+            _f(py::cast(&_U, py::return_value_policy::reference), py::cast(&_change, py::return_value_policy::reference));
+        };
+    };
+    auto transport = [](py::object _f) -> TTVectorTransport {
+        return [_f](const TTTensor& _newBase, TTTangentVector& _v) {
+            _f(py::cast(&_newBase, py::return_value_policy::reference), py::cast(&_v, py::return_value_policy::reference));
+        };
+    };
+
+    py::class_<SteepestDescentVariant>(m, "SteepestDescentVariant")
+        .def(py::init([retractionII](size_t _numSteps, value_t _eps, bool _symPosOp, py::object _retraction) {
+                 return SteepestDescentVariant(_numSteps, _eps, _symPosOp, retractionII(_retraction));
+             }),
+             py::arg("numSteps"), py::arg("convergenceEpsilon"), py::arg("symPosOp"), py::arg("retraction"))
+        .def(py::init([retractionII](py::object _retraction) { return SteepestDescentVariant(retractionII(_retraction)); }),
+             py::arg("retraction"))
+        .def_readwrite("numSteps", &SteepestDescentVariant::numSteps)
+        .def_readwrite("convergenceEpsilon", &SteepestDescentVariant::convergenceEpsilon)
+        .def_readwrite("assumeSymmetricPositiveDefiniteOperator", &SteepestDescentVariant::assumeSymmetricPositiveDefiniteOperator)
+        .def_property("preconditioner",
+                      py::cpp_function([](const SteepestDescentVariant& _s) { return _s.preconditioner; },
+                                       py::return_value_policy::reference),
+                      py::cpp_function([](SteepestDescentVariant& _s, TTOperator* _p) { _s.preconditioner = _p; },
+                                       py::keep_alive<1, 2>()))
+        .def_property("retraction", [](const SteepestDescentVariant& _s) { return _s.retraction; },
+                      [retractionII](SteepestDescentVariant& _s, py::object _f) { _s.retraction = retractionII(_f); })
+        .def("__call__", [](const SteepestDescentVariant& _s, const TTOperator& _A, TTTensor& _x, const TTTensor& _b, value_t _eps) {
+            return _s(_A, _x, _b, _eps);
+        })
+        .def("__call__", [](const SteepestDescentVariant& _s, const TTOperator& _A, TTTensor& _x, const TTTensor& _b, size_t _n) {
+            return _s(_A, _x, _b, _n);
+        })
+        .def("__call__",
+             [](const SteepestDescentVariant& _s, const TTOperator& _A, TTTensor& _x, const TTTensor& _b) { return _s(_A, _x, _b); })
+        .def("__call__", [](const SteepestDescentVariant& _s, TTTensor& _x, const TTTensor& _b, value_t _eps) { return _s(_x, _b, _eps); })
+        .def("__call__", [](const SteepestDescentVariant& _s, TTTensor& _x, const TTTensor& _b, size_t _n) { return _s(_x, _b, _n); })
+        .def("__call__", [](const SteepestDescentVariant& _s, TTTensor& _x, const TTTensor& _b) { return _s(_x, _b); })
+        .def("__copy__", [](const SteepestDescentVariant& _s) { return SteepestDescentVariant(_s); });
+    m.attr("SteepestDescent") = py::cast(SteepestDescentVariant(SteepestDescent));
+
+    py::class_<GeometricCGVariant>(m, "GeometricCGVariant")
+        .def(py::init([retractionI, transport](size_t _numSteps, value_t _eps, bool _symPosOp, py::object _retraction,
+                                               py::object _transport) {
+                 return GeometricCGVariant(_numSteps, _eps, _symPosOp, retractionI(_retraction), transport(_transport));
+             }),
+             py::arg("numSteps"), py::arg("convergenceEpsilon"), py::arg("symPosOp"), py::arg("retraction"),
+             py::arg("vectorTransport"))
+        .def(py::init([retractionI, transport](py::object _retraction, py::object _transport) {
+                 return GeometricCGVariant(retractionI(_retraction), transport(_transport));
+             }),
+             py::arg("retraction"), py::arg("vectorTransport"))
+        .def_readwrite("numSteps", &GeometricCGVariant::numSteps)
+        .def_readwrite("convergenceEpsilon", &GeometricCGVariant::convergenceEpsilon)
+        .def_readwrite("assumeSymmetricPositiveDefiniteOperator", &GeometricCGVariant::assumeSymmetricPositiveDefiniteOperator)
+        .def_property("retraction", [](const GeometricCGVariant& _s) { return _s.retraction; },
+                      [retractionI](GeometricCGVariant& _s, py::object _f) { _s.retraction = retractionI(_f); })
+        .def_property("vectorTransport", [](const GeometricCGVariant& _s) { return _s.vectorTransport; },
+                      [transport](GeometricCGVariant& _s, py::object _f) { _s.vectorTransport = transport(_f); })
+        .def("__call__", [](const GeometricCGVariant& _s, const TTOperator& _A, TTTensor& _x, const TTTensor& _b, value_t _eps) {
+            return _s(_A, _x, _b, _eps);
+        })
+        .def("__call__", [](const GeometricCGVariant& _s, const TTOperator& _A, TTTensor& _x, const TTTensor& _b, size_t _n) {
+            return _s(_A, _x, _b, _n);
+        })
+        .def("__call__", [](const GeometricCGVariant& _s, const TTOperator& _A, TTTensor& _x, const TTTensor& _b) { return _s(_A, _x, _b); })
+        .def("__call__", [](const GeometricCGVariant& _s, TTTensor& _x, const TTTensor& _b, value_t _eps) { return _s(_x, _b, _eps); })
+        .def("__call__", [](const GeometricCGVariant& _s, TTTensor& _x, const TTTensor& _b, size_t _n) { return _s(_x, _b, _n); })
+        .def("__call__", [](const GeometricCGVariant& _s, TTTensor& _x, const TTTensor& _b) { return _s(_x, _b); })
+        .def("__copy__", [](const GeometricCGVariant& _s) { return GeometricCGVariant(_s); });
+    m.attr("GeometricCG") = py::cast(GeometricCGVariant(GeometricCG));
 
     // ------------------------------------------------------------------ measurements + ADF (measurments.h, algorithms/adf.h)
     py::class_<SinglePointMeasurementSet>(m, "SinglePointMeasurementSet")

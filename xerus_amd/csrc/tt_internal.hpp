@@ -13,6 +13,14 @@ double dot(xrs_handle_t h, size_t d, const size_t* n, const size_t* rx, const do
            const double* const* Y);
 void soft_threshold(xrs_handle_t h, size_t d, const size_t* n, size_t* r, double** cores, bool canonicalized, size_t core_pos,
                     const double* taus);
+// tangent.hip: the tangent-space projection, the block TT of a tangent vector and the weighted inner product
+// (xrs_tt_tangent_project / _to_tt / _dot); outputs are new buffers of the handle's pool
+void tangent_project(xrs_handle_t h, size_t d, const size_t* n, const size_t* ru, const double* const* U, const size_t* rz,
+                     const double* const* Z, double** V, double** UU, size_t* fallback_edges);
+void tangent_to_tt(xrs_handle_t h, size_t d, const size_t* n, const size_t* r, const double* const* U, const double* const* V,
+                   bool add_base, double** out);
+double tangent_dot(xrs_handle_t h, size_t d, const size_t* n, const size_t* r, const double* const* UU, const double* const* A,
+                   const double* const* B);
 }  // namespace tt
 namespace zip {   // zip32.hip: the fused fp32 zipper (xrs_tt_dot_f32's main path)
 bool applicable(size_t d, const size_t* n, const size_t* rx, const double* const* X, const size_t* ry,
