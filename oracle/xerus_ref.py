@@ -23,6 +23,7 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 from scipy.linalg import lapack
+from scipy.linalg.blas import dnrm2 as _dnrm2
 
 DBL_EPSILON = float(np.finfo(np.float64).eps)
 EPSILON = 8 * DBL_EPSILON  # include/xerus/basic.h:51
@@ -364,7 +365,9 @@ class TT:
     def frob_norm(self) -> float:
         """ttNetwork.cpp:782-789."""
         if self.canonicalized:
-            return float(np.linalg.norm(self.cores[self.core_position]))
+            # blasWrapper::two_norm = cblas_dnrm2: scaled, so no overflow / underflow of the squares
+            core = np.ascontiguousarray(self.cores[self.core_position], dtype=np.float64)
+            return float(_dnrm2(core.ravel()))
         return float(np.sqrt(max(0.0, dot(self, self))))
 
 

@@ -26,8 +26,10 @@ pytestmark = pytest.mark.gpu
     ([20] * 12, [256] * 11, 1.0),                    # cfg4 shape
     ([20] * 10, [64] * 9, 1e6),                      # ||x|| ~ 1e66: beyond fp32 without the renormalisation
     ([20] * 10, [64] * 9, 1e-6),                     # ||x|| ~ 1e-54
-    # the fused zipper (zip32.hip): heads only (d = 4), one end without a step (d = 5), uneven step counts
-    # (d = 7), the headline shape at other scales (per-unit T exponents, exponent words)
+    # shapes chosen for the fused zipper's structure (heads only, d = 4; one end without a step, d = 5; uneven
+    # step counts, d = 7; the headline shape at other scales). The fused zipper is opt-in (XRS_ZIP32): with it
+    # unset, as here, these run the per-product launches of dot32.hip; zip32.hip itself is reached only by
+    # test_dot_f32_fused_matches_per_product_form's subprocesses
     ([20] * 4, [20, 128, 20], 1.0),
     ([8] * 5, [8, 64, 64, 8], 1.0),
     ([10] * 7, [10, 96, 96, 96, 96, 10], 1.0),
@@ -87,12 +89,13 @@ def test_dot_f32_correlated(handle, ref, dims, ranks):
 @pytest.mark.parametrize("scale,d", [(1e-40, 3), (1e40, 3), (1e-25, 4), (1e25, 4), (1e9, 4), (1e-15, 4),
                                      (1e-12, 6), (1e12, 6), (1e9, 6), (1e-15, 6)])
 def test_dot_f32_core_range(handle, ref, scale, d):
-    """Both TTs' cores scaled (d = 6 through the fused zipper's fp32 steps, where 1e+-40 would leave
-    the fp64 range of the reference value itself): 1e+-40 lies outside the fp32 zipper's core range [2^-100, 2^100) and
+    """Both TTs' cores scaled (d = 6 has fp32 steps between the heads, where 1e+-40 would leave
+    the fp64 range of the reference value itself; with XRS_ZIP32 unset these are dot32.hip's per-product
+    launches, not the fused zipper): 1e+-40 lies outside the fp32 zipper's core range [2^-100, 2^100) and
     must come back as the fp64 result (the fp64 zipper takes over); 1e+-25, 1e9, 1e-15 lie inside and run in
     fp32 at fp32 accuracy (every product has one raw core and one power-of-two normalised operand)."""
     rng = ref.Rng(31)
-    # d = 6: ranks 20 / 64 (x + z: 40 / 128), the fused zipper's heads and fp32 steps (zip32.hip)
+    # d = 6: ranks 20 / 64 (x + z: 40 / 128): heads and fp32 steps (the shapes the fused zipper would take)
     dims, ranks = [20] * d, ([20] * (d - 1) if d < 6 else [20] + [64] * (d - 3) + [20])
     x = ref.TT.random_raw(dims, ranks, rng)
     z = ref.TT.random_raw(dims, ranks, rng)

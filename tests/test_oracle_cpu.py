@@ -102,3 +102,17 @@ def test_tt_dot_oracle(ref):
     y = ref.TT.random([3, 4, 3, 2], [3, 2, 2], rng)
     assert np.isclose(ref.dot(x, y), float(np.sum(x.full() * y.full())), rtol=1e-12, atol=1e-12)
     assert np.isclose(x.frob_norm(), np.linalg.norm(x.full()), rtol=1e-12)
+
+
+@pytest.mark.parametrize("e", [600, -600])
+def test_tt_frob_norm_canonicalised_is_scaled(ref, e):
+    """The canonicalised frob_norm is the reference's two_norm (cblas_dnrm2) of the core: with one core at
+    2^e the squares of the entries overflow / underflow, the norm is exactly 2^e times the unscaled one."""
+    x = ref.TT.random_raw([6] * 5, [8] * 4, ref.Rng(41))
+    y = x.copy()
+    y.cores[2] = np.ldexp(y.cores[2], e)
+    x.move_core(0)
+    y.move_core(0)
+    n0, n1 = x.frob_norm(), y.frob_norm()
+    assert np.isfinite(n1) and n1 > 0.0
+    assert abs(np.ldexp(n1, -e) - n0) <= 1e-12 * n0

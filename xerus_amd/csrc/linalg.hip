@@ -277,8 +277,7 @@ static void compact_cols(xrs_handle_t h, double* dst, size_t ldd, const double* 
     XRS_HIP(hipMemcpy2DAsync(dst, ldd * 8, src, lds * 8, cols * 8, rows, hipMemcpyDeviceToDevice, h->stream));
 }
 
-size_t qc(xrs_handle_t h, const double* A, size_t m, size_t n, double* Q, double* C) {
-    XRS_REQUIRE(m > 0 && n > 0, "Dimension m and n must be larger than zero");
+static size_t qc_core(xrs_handle_t h, const double* A, size_t m, size_t n, double* Q, double* C) {
     const size_t k = std::min(m, n);
     auto exact = [&] {   // the dgeqp3 emulation on A itself
         DevBuf Qf(h, m * k * 8);
@@ -303,8 +302,7 @@ size_t qc(xrs_handle_t h, const double* A, size_t m, size_t n, double* Q, double
 }
 
 // CQ: the reference runs col-major dgeqp3 on A^T (blasLapackWrapper.cpp:317-371), i.e. QC of A^T.
-size_t cq(xrs_handle_t h, const double* A, size_t m, size_t n, double* C, double* Q) {
-    XRS_REQUIRE(m > 0 && n > 0, "Dimension m and n must be larger than zero");
+static size_t cq_core(xrs_handle_t h, const double* A, size_t m, size_t n, double* C, double* Q) {
     const size_t k = std::min(m, n);
     auto exact = [&] {
         DevBuf At(h, m * n * 8), Qt(h, n * k * 8), Ct(h, k * m * 8);
@@ -328,8 +326,7 @@ size_t cq(xrs_handle_t h, const double* A, size_t m, size_t n, double* C, double
     return exact();   // (see qc)
 }
 
-void qr(xrs_handle_t h, const double* A, size_t m, size_t n, double* Q, double* R) {
-    XRS_REQUIRE(m > 0 && n > 0, "Dimension m and n must be larger than zero");
+static void qr_core(xrs_handle_t h, const double* A, size_t m, size_t n, double* Q, double* R) {
     if (m >= n && !small_problem(m, n)) {
         try {
             orthogonalize(h, A, m, n, false, Q, R);
@@ -341,8 +338,7 @@ void qr(xrs_handle_t h, const double* A, size_t m, size_t n, double* Q, double* 
     qrcp(h, A, m, n, Q, R, false, false, false);
 }
 
-void rq(xrs_handle_t h, const double* A, size_t m, size_t n, double* R, double* Q) {
-    XRS_REQUIRE(m > 0 && n > 0, "Dimension m and n must be larger than zero");
+static void rq_core(xrs_handle_t h, const double* A, size_t m, size_t n, double* R, double* Q) {
     if (m <= n && !small_problem(m, n)) {
         try {
             orthogonalize(h, A, m, n, true, Q, R);
@@ -357,6 +353,61 @@ void rq(xrs_handle_t h, const double* A, size_t m, size_t n, double* R, double* 
     qrcp(h, At.d(), n, m, Qt.d(), Rt.d(), false, false, false);   // A^T = Qt Rt
     transpose(h, Q, Qt.d(), n, k);
     transpose(h, R, Rt.d(), k, m);
+}
+
+// Range-controlled entry points (see elementwise.hpp): an input with max |A| outside [2^-200, 2^200] is
+// factorised as A 2^-ex, ex = ilogb(max |A|), and the triangular factor scaled back by 2^ex. Both scalings are
+// exact, so the orthogonal factor, the rank rule (relative: |R_kk| < 16 eps R_00) and the certificates are those
+// of an input of ordinary size. (Unscaled, the Gram A^T A of 1e+-180-sized entries is inf / 0: the shifted
+// Cholesky passes fail and the Householder emulation's column norms overflow as well.)
+// No synchronisation of its own: max |A| is enqueued ahead of the factorisation and read behind the host wait
+// every route already has (the Cholesky statuses, qrcp's rank). Only an out-of-range input, whose first attempt
+// holds no iterative kernel (bounded column loops) and whose result is discarded, is factorised a second time.
+template <class Run, class Back>
+static auto range_controlled(xrs_handle_t h, const double* A, size_t count, Run run, Back scale_back) {
+    double* am_dev = static_cast<double*>(h->dev_scratch) + 49;
+    double* am_host = static_cast<double*>(h->host_scratch) + 49;
+    amax_enqueue(h, &A, &count, 1, am_dev);
+    XRS_HIP(hipMemcpyAsync(am_host, am_dev, 8, hipMemcpyDeviceToHost, h->stream));
+    auto exponent = [&] { return range_exponent(am_host[0]); };
+    decltype(run(A)) r{};
+    try {
+        r = run(A);   // (synchronises at least once)
+        if (exponent() == 0) return r;
+    } catch (const Error&) {
+        XRS_HIP(hipStreamSynchronize(h->stream));
+        if (exponent() == 0) throw;
+    }
+    const int ex = exponent();
+    DevBuf As(h, count * 8);
+    ldexp_copy(h, As.d(), A, -ex, count);
+    r = run(As.d());
+    scale_back(r, ex);
+    return r;
+}
+
+size_t qc(xrs_handle_t h, const double* A, size_t m, size_t n, double* Q, double* C) {
+    XRS_REQUIRE(m > 0 && n > 0, "Dimension m and n must be larger than zero");
+    return range_controlled(h, A, m * n, [&](const double* X) { return qc_core(h, X, m, n, Q, C); },
+                            [&](size_t r, int ex) { ldexp_copy(h, C, C, ex, r * n); });
+}
+
+size_t cq(xrs_handle_t h, const double* A, size_t m, size_t n, double* C, double* Q) {
+    XRS_REQUIRE(m > 0 && n > 0, "Dimension m and n must be larger than zero");
+    return range_controlled(h, A, m * n, [&](const double* X) { return cq_core(h, X, m, n, C, Q); },
+                            [&](size_t r, int ex) { ldexp_copy(h, C, C, ex, m * r); });
+}
+
+void qr(xrs_handle_t h, const double* A, size_t m, size_t n, double* Q, double* R) {
+    XRS_REQUIRE(m > 0 && n > 0, "Dimension m and n must be larger than zero");
+    range_controlled(h, A, m * n, [&](const double* X) { qr_core(h, X, m, n, Q, R); return 0; },
+                     [&](int, int ex) { ldexp_copy(h, R, R, ex, std::min(m, n) * n); });
+}
+
+void rq(xrs_handle_t h, const double* A, size_t m, size_t n, double* R, double* Q) {
+    XRS_REQUIRE(m > 0 && n > 0, "Dimension m and n must be larger than zero");
+    range_controlled(h, A, m * n, [&](const double* X) { rq_core(h, X, m, n, R, Q); return 0; },
+                     [&](int, int ex) { ldexp_copy(h, R, R, ex, m * std::min(m, n)); });
 }
 
 // U[:, j] *= 1 / S[j] (0 for S[j] == 0): U = R V S^{-1}
@@ -395,27 +446,6 @@ static void svd_big(xrs_handle_t h, const double* A, size_t m, size_t n, double*
     orthogonalize(h, Uq.d(), m, n, false, U, Rn.d());
 }
 
-__global__ void __launch_bounds__(1024) k_amax(const double* __restrict__ x, size_t n, double* __restrict__ out) {
-    __shared__ double red[16];
-    double mx = 0.0;
-    for (size_t e = threadIdx.x; e < n; e += 1024) {
-        const double d = fabs(x[e]);
-        mx = (d > mx || d != d) ? d : mx;   // NaN propagates
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double t = __shfl_xor(mx, o, 64);
-        mx = (t > mx || t != t) ? t : mx;
-    }
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double v = red[0];
-        for (int i = 1; i < 16; ++i) v = (red[i] > v || red[i] != red[i]) ? red[i] : v;
-        out[0] = v;
-    }
-}
-
 static void svd_core(xrs_handle_t h, const double* A, size_t m, size_t n, double* U, double* S, double* Vt);
 
 // the bidiagonal route (syev.hip svd_bidiag) on a square n x n A; false: run the Jacobi route (XRS_SVD_BIDIAG=2:
@@ -438,21 +468,14 @@ void svd(xrs_handle_t h, const double* A, size_t m, size_t n, double* U, double*
     if (m == n && n >= 16 && n <= 128 && svd_bidiag_mode() != 0 && try_bidiag(h, A, n, U, S, Vt)) return;
     // range control, dgesdd's dlascl of A into [smlnum, bignum] (here by an exact power of two, to max |A| ~ 1):
     // the Gram-based preconditioning and the Jacobi dots square the entries (unscaled, 1e150-sized entries
-    // overflowed them)
-    double* am_dev = static_cast<double*>(h->dev_scratch) + 48;
-    hipLaunchKernelGGL(k_amax, dim3(1), dim3(1024), 0, h->stream, A, m * n, am_dev);
-    check_launch("k_amax");
-    double* am_host = static_cast<double*>(h->host_scratch) + 48;
-    XRS_HIP(hipMemcpyAsync(am_host, am_dev, 8, hipMemcpyDeviceToHost, h->stream));
-    XRS_HIP(hipStreamSynchronize(h->stream));
-    const double am = am_host[0];
-    if (am > 0.0 && std::isfinite(am) && (am > 0x1p+200 || am < 0x1p-200)) {
-        const int ex = std::ilogb(am);
+    // overflowed them). The power of two is applied by ldexp on the entries: 2^-ex itself is not representable
+    // for a subnormal max |A| (ex < -1023).
+    const int ex = range_exponent(h, A, m * n);
+    if (ex != 0) {
         DevBuf As(h, m * n * 8);
-        XRS_HIP(hipMemcpyAsync(As.d(), A, m * n * 8, hipMemcpyDeviceToDevice, h->stream));
-        scal(h, As.d(), std::ldexp(1.0, -ex), m * n);
+        ldexp_copy(h, As.d(), A, -ex, m * n);
         svd_core(h, As.d(), m, n, U, S, Vt);
-        scal(h, S, std::ldexp(1.0, ex), std::min(m, n));
+        ldexp_copy(h, S, S, ex, std::min(m, n));
         return;
     }
     svd_core(h, A, m, n, U, S, Vt);
@@ -476,11 +499,11 @@ static void svd_core(xrs_handle_t h, const double* A, size_t m, size_t n, double
     //   wide A = R Q: R = U S Vr, Vt = Vr Q;   tall A = Q R: R = U_R S Vt, U = Q U_R
     DevBuf R(h, k * k * 8), Qf(h, m * n * 8), F(h, k * k * 8);
     if (m <= n) {
-        rq(h, A, m, n, R.d(), Qf.d());
+        rq_core(h, A, m, n, R.d(), Qf.d());   // (A is range-controlled already)
         if (!(bd && try_bidiag(h, R.d(), k, U, S, F.d()))) jacobi_svd_rows(h, R.d(), int(k), int(k), U, S, F.d());
         gemm(h, Vt, k, n, 1.0, F.d(), k, false, k, Qf.d(), n, false);
     } else {
-        qr(h, A, m, n, Qf.d(), R.d());
+        qr_core(h, A, m, n, Qf.d(), R.d());
         if (!(bd && try_bidiag(h, R.d(), k, F.d(), S, Vt))) jacobi_svd_rows(h, R.d(), int(k), int(k), F.d(), S, Vt);
         gemm(h, U, m, k, 1.0, Qf.d(), k, false, k, F.d(), k, false);
     }
@@ -537,9 +560,16 @@ int xrs_sym_eig_top(xrs_handle_t h, double* lam, double* Ut, int* status, const 
         XRS_REQUIRE(h && lam && Ut && status && A, "null argument");
         XRS_REQUIRE(n >= 2 && n <= 256 && kk >= 1 && kk <= n, "xrs_sym_eig_top: need 2 <= n <= 256 and 1 <= kk <= n");
         fence_readers(h);
-        DevBuf st(h, 64);
+        DevBuf st(h, 64), As;
         XRS_HIP(hipMemsetAsync(st.d(), 0, 64, h->stream));
-        sym_eig_top(h, A, int(n), int(n), int(kk), lam, nullptr, Ut, int(n), st.as<int>());
+        // (range control: the tridiagonalisation's reflector norms and the Sturm counts square the entries)
+        const int ex = range_exponent(h, A, n * n);
+        if (ex != 0) {
+            As = DevBuf(h, n * n * 8);
+            ldexp_copy(h, As.d(), A, -ex, n * n);
+        }
+        sym_eig_top(h, ex != 0 ? As.d() : A, int(n), int(n), int(kk), lam, nullptr, Ut, int(n), st.as<int>());
+        ldexp_copy(h, lam, lam, ex, kk);
         read_status(h, st.as<int>(), 1, status);
     });
 }
@@ -559,9 +589,15 @@ int xrs_svd_rows_vt(xrs_handle_t h, double* S, double* Vt, int* sweeps, const do
         XRS_REQUIRE(h && S && Vt && A && sweeps, "null argument");
         XRS_REQUIRE(p >= 1 && p <= q && q <= 1024 && (kernel != 1 || p <= 512),
                     "xrs_svd_rows_vt: need 1 <= p <= q <= 1024 (kernel 1: p <= 512)");
-        DevBuf st(h, 64);
+        DevBuf st(h, 64), As;
         XRS_HIP(hipMemsetAsync(st.d(), 0, 64, h->stream));
-        jacobi_vt(h, A, int(q), false, int(p), int(q), S, Vt, int(q), st.as<int>(), 40, kernel, stamps_enabled("svd"));
+        const int ex = range_exponent(h, A, p * q);   // (range control: the Jacobi dots square the entries)
+        if (ex != 0) {
+            As = DevBuf(h, p * q * 8);
+            ldexp_copy(h, As.d(), A, -ex, p * q);
+        }
+        jacobi_vt(h, ex != 0 ? As.d() : A, int(q), false, int(p), int(q), S, Vt, int(q), st.as<int>(), 40, kernel, stamps_enabled("svd"));
+        ldexp_copy(h, S, S, ex, p);
         int sts[9];
         read_status(h, st.as<int>(), 9, sts);
         *sweeps = sts[0];

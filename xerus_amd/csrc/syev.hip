@@ -973,11 +973,11 @@ __global__ void __launch_bounds__(512) k_gebrd_sq(const double* __restrict__ A, 
 #pragma unroll
     for (int w = 1; w < 8; ++w) am = fmax(am, red[w]);
     const int ex = am > 0.0 ? ilogb(am) : 0;
-    const double sdn = ldexp(1.0, -ex), sup = ldexp(1.0, ex);
+    // (ldexp on the entries themselves: 2^-ex is not representable for a subnormal max |A|, ex < -1023)
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) x[i][k] *= sdn;
+        for (int k = 0; k < 4; ++k) x[i][k] = ldexp(x[i][k], -ex);
     BD_STAMP(1);
     for (int j = 0; j < n; ++j) {
         BD_STAMP(4 + 4 * j);
@@ -1011,7 +1011,7 @@ __global__ void __launch_bounds__(512) k_gebrd_sq(const double* __restrict__ A, 
                 vbuf[r] = y[i];
             }
             if (rho == 0) {
-                obuf[0][j] = beta * sup;
+                obuf[0][j] = ldexp(beta, ex);
                 obuf[2][j] = tau;
                 stau = tau;
             }
@@ -1091,7 +1091,7 @@ __global__ void __launch_bounds__(512) k_gebrd_sq(const double* __restrict__ A, 
             vc[k] = c >= j + 2 ? xbuf[c] * scr : (c == j + 1 ? 1.0 : 0.0);
         }
         if (tid == 0) {
-            obuf[1][j] = betr * sup;
+            obuf[1][j] = ldexp(betr, ex);
             obuf[3][j] = taur;
         }
         if (taur != 0.0) {   // (uniform)
@@ -1228,10 +1228,10 @@ __global__ void __launch_bounds__(1024) k_svd_check(const double* __restrict__ P
         samax = v;
     }
     __syncthreads();
-    const double s = samax > 0.0 ? ldexp(1.0, -ilogb(samax)) : 1.0;
+    const int sex = samax > 0.0 ? -ilogb(samax) : 0;   // (applied by ldexp: 2^sex overflows for a subnormal max |A|)
     double r2 = 0.0, a2 = 0.0, m1 = 0.0, m2 = 0.0;
     for (int e = threadIdx.x; e < n * n; e += 1024) {
-        const double d = (P[e] - A[e]) * s, as = A[e] * s, id = (e / n == e % n) ? 1.0 : 0.0;
+        const double d = ldexp(P[e] - A[e], sex), as = ldexp(A[e], sex), id = (e / n == e % n) ? 1.0 : 0.0;
         r2 = fma(d, d, r2);
         a2 = fma(as, as, a2);
         const double g1 = fabs(G1[e] - id), g2 = fabs(G2[e] - id);

@@ -856,21 +856,102 @@ void rl_sweep(TT& t, const size_t* max_ranks, double eps, double cX, size_t from
     }
 }
 
+// pinned / device scratch of the range probe (slots no other routine uses)
+constexpr size_t kProbeMax = 960, kProbeHost = 7200, kProbeDev = 4096;
+
+void probe_core_ranges(TT& t) {
+    t.range_probed = false;
+    if (t.sharded() || t.d > kProbeMax) return;   // (sharded: the ranks would have to agree on the exponents)
+    xrs_handle_t h = t.h;
+    std::vector<const double*> x(t.core, t.core + t.d);
+    std::vector<size_t> n(t.d);
+    for (size_t k = 0; k < t.d; ++k) n[k] = t.size(k);
+    double* dev = static_cast<double*>(h->dev_scratch) + kProbeDev;
+    norms_enqueue(h, x.data(), n.data(), int(t.d), dev);
+    XRS_HIP(hipMemcpyAsync(static_cast<double*>(h->host_scratch) + kProbeHost, dev, t.d * 8, hipMemcpyDeviceToHost, h->stream));
+    t.range_probed = true;
+}
+
+// ex[k] = ilogb of core k's scale from the probe (0 for a zero or non-finite core): its Frobenius norm over the
+// root of the rank of its unfoldings, which is 1 for an orthonormal core of a canonical TT, whatever its
+// size, and the rms singular value otherwise. True when the exponents of some run of neighbouring cores add up
+// to more than 200 in magnitude (2^+-200 ~ 1e+-60): the scale a sweep or a Gram chain gathers in one factor,
+// which the Grams and the Jacobi dots then square
+static bool core_exponents(const TT& t, std::vector<int>& ex) {
+    const double* am = static_cast<const double*>(t.h->host_scratch) + kProbeHost;
+    ex.assign(t.d, 0);
+    long prefix = 0, lo = 0, hi = 0;   // (largest |sum over a run| = max prefix sum - min prefix sum)
+    for (size_t k = 0; k < t.d; ++k) {
+        const size_t rank = std::max(std::min(t.rows_left(k), t.r[k + 1]), std::min(t.r[k], t.cols_right(k)));
+        if (am[k] > 0.0 && std::isfinite(am[k])) {
+            // (the norm's exponent first: dividing a subnormal or near-largest norm would round or overflow)
+            int e2 = 0;
+            const double mant = std::frexp(am[k], &e2);
+            ex[k] = e2 + std::ilogb(mant / std::sqrt(double(rank)));
+        }
+        prefix += ex[k];
+        lo = std::min(lo, prefix);
+        hi = std::max(hi, prefix);
+    }
+    return hi - lo > 200;
+}
+
+bool core_range_exceeded(const TT& t) {
+    if (!t.range_probed) return false;
+    std::vector<int> ex;
+    return core_exponents(t, ex);
+}
+
+static void round_ranged(TT& t, bool canonicalized, size_t core_pos, const size_t* max_ranks, double eps, bool probe);
+
 void round(TT& t, bool canonicalized, size_t core_pos, const size_t* max_ranks, double eps) {
+    round_ranged(t, canonicalized, core_pos, max_ranks, eps, true);
+}
+
+static void round_ranged(TT& t, bool canonicalized, size_t core_pos, const size_t* max_ranks, double eps, bool probe) {
     const size_t d = t.d;
     t.h->last_round_path = XRS_ROUND_CHAIN;
-    if (round_chain(t, max_ranks, eps)) return;      // certified, nothing to cut
+    // certified, nothing to cut. (No range probe ahead of it: the pass holds no iterative kernel, its Cholesky
+    // factorisations report an inf / NaN / zero Gram, and the check rejects what they let through.)
+    if (round_chain(t, max_ranks, eps)) return;
+    t.range_probed = t.range_hit = false;
+    if (probe && d >= 2) probe_core_ranges(t);   // enqueued only: read behind the next host wait
     t.h->last_round_path = XRS_ROUND_TRUNCATE;
     if (round_truncate(t, max_ranks, eps)) return;   // certified, cuts by maxRank only (tt_trunc.hip)
     static const bool no_general = std::getenv("XRS_NO_GENERAL_ROUND") != nullptr;
     t.h->last_round_path = XRS_ROUND_GENERAL;
-    if (!no_general && round_general(t, max_ranks, eps)) return;   // any spectrum, device-resident (tt_trunc.hip)
+    if (!t.range_hit && !no_general && round_general(t, max_ranks, eps)) return;   // any spectrum, device-resident (tt_trunc.hip)
+    if (t.range_probed && !t.range_hit) {   // (both declined before their first host wait)
+        host_wait(t.h);
+        t.range_hit = core_range_exceeded(t);
+    }
+    if (t.range_hit) {
+        // cores to scale ~ 1 by exact powers of two, the round once more, their product to the core at 0: the result
+        // is canonical there, so that core's norm is the tensor's
+        // (probed afresh: a round that gave up may have removed a structural excess at the left end first)
+        std::vector<int> ex;
+        probe_core_ranges(t);
+        host_wait(t.h);
+        core_exponents(t, ex);
+        t.range_probed = t.range_hit = false;
+        long total = 0;
+        for (size_t k = 0; k < d; ++k) {
+            if (ex[k] == 0) continue;
+            double* c = t.alloc(t.size(k));
+            ldexp_copy(t.h, c, t.core[k], -ex[k], t.size(k));
+            t.replace(k, c);
+            total += ex[k];
+        }
+        round_ranged(t, canonicalized, core_pos, max_ranks, eps, false);
+        // (beyond the range of a double the entries become inf / 0, as the tensor's own norm would)
+        ldexp_copy(t.h, t.core[0], t.core[0], int(std::max(-4000L, std::min(4000L, total))), t.size(0));
+        return;
+    }
+    t.range_probed = false;
     t.h->last_round_path = XRS_ROUND_REFERENCE;
     // canonicalize_right (ttNetwork.cpp:638-640, 654)
     const size_t start = canonicalized ? core_pos : 0;
     for (size_t k = start; k + 1 < d; ++k) orth_right(t, k);
-    if (!canonicalized)
-        ;  // cores 0..d-2 are now left-orthogonal
     // right-to-left truncation (ttNetwork.cpp:656-658)
     for (size_t k = d - 1; k >= 1; --k) truncate_edge(t, k, max_ranks[k - 1], eps);
 }

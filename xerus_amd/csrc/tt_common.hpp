@@ -47,6 +47,9 @@ struct TT {
     std::vector<size_t> layout_ng, layout_off;
     bool layout_known = false;
     bool sharded() const { return shard_mode; }
+    // round(): the norm of every core is on its way to the handle's pinned scratch (probe_core_ranges)
+    bool range_probed = false;
+    bool range_hit = false;      // a device-resident round gave up on it (core_range_exceeded behind its host wait)
     void reduce(double* buf, size_t count) const {
         if (!ar) return;
         // the built-in RCCL hook is stream-ordered; any other hook sees a synchronised stream
@@ -71,6 +74,18 @@ void remove_left_excess(TT& t, const ShardLayout& lay);
 // reduce_to_maximal_ranks (ttNetwork.cpp:370-402) of the internal ranks; true if any rank exceeds it
 std::vector<size_t> maximal_ranks(const TT& t);
 bool exceeds_maximal_ranks(const TT& t);
+
+// Range control of round() (tt.hip). The Gram chains multiply the squares of all cores, and a sweep gathers the
+// scale of every core it has passed in one, so a TT whose cores' exponents add up to 2^+-300 is far outside
+// them although each core, and the tensor, is representable. probe_core_ranges enqueues the norm of every
+// core and its copy to pinned host memory, without a synchronisation; core_range_exceeded reads it after the
+// caller's next host wait: true when the exponents of the cores' scales (norm over the root of the unfolding
+// rank: 0 for the orthonormal cores of a canonical TT) summed over some run of neighbouring cores exceed 200
+// in magnitude -- the device-resident rounds then give up (range_hit) before their iterative kernels see
+// inf / NaN, and round() repeats itself on cores brought to scale ~ 1 by exact powers of two, whose product
+// it gives back to core 0.
+void probe_core_ranges(TT& t);
+bool core_range_exceeded(const TT& t);
 
 // relative downward shift of the certifying Cholesky factorisations (see tt.hip, round_chain)
 constexpr double kGramShift = 1e-11;

@@ -381,6 +381,11 @@ bool round_truncate(TT& t, const size_t* max_ranks, double eps) {
         XRS_HIP(hipMemcpyAsync(hs, status, size_t(nst) * 4, hipMemcpyDeviceToHost, h->stream));
         XRS_HIP(hipMemcpyAsync(hd, devb.d(), size_t(nchk) * 8, hipMemcpyDeviceToHost, h->stream));
         host_wait(h);
+        if (core_range_exceeded(t)) {   // (round(): repeated on range-controlled cores)
+            t.range_hit = true;
+            sw.discard();
+            return false;
+        }
         bool ok = true;
         for (int i = 0; i < nst; ++i) ok = ok && hs[i] == 0;
         worst = 0.0;
@@ -817,6 +822,11 @@ bool round_general(TT& t, const size_t* max_ranks, double eps) {
         XRS_HIP(hipMemcpyAsync(hs, st, size_t(cst) * 4, hipMemcpyDeviceToHost, h->stream));
         XRS_HIP(hipMemcpyAsync(hd, devb.d(), size_t(nchk) * 8, hipMemcpyDeviceToHost, h->stream));
         host_wait(h);
+        if (core_range_exceeded(t)) {   // (round(): repeated on range-controlled cores)
+            t.range_hit = true;
+            sw.discard();
+            return false;
+        }
         chain_ok = true;
         int first_bad = -1;
         for (int i = 0; i < cst; ++i)
