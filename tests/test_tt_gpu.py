@@ -288,7 +288,7 @@ def test_round_bench_shape(handle, ref):
 
 @pytest.mark.parametrize("ranks", [[20, 400, 400, 20], [20, 300, 300, 20]])
 def test_round_ranks_above_256(handle, ref, ranks):
-    """Edges with 256 < r <= 512 factor through the 2 x 2-block Cholesky (factor_big): certified path,
+    """Edges with 256 < r <= 512 factor through the 2 x 2-block Cholesky (chol_batch.hip): certified path,
     exact ranks, right-orthonormal cores, same tensor as the input."""
     rng = ref.Rng(29)
     x = ref.TT.random_raw([20] * 5, ranks, rng)
@@ -314,8 +314,8 @@ def test_tt_errors(handle, ref):
 
 
 def test_round_many_edges_above_256(handle, ref):
-    """Order 25, rank 300: 22 edges with 256 < r <= 512 need 66 factor_big jobs in the certified pass,
-    more than one argument table holds (kBigMax = 64): the jobs go out in chunks."""
+    """Order 25, rank 300: 22 edges with 256 < r <= 512 need 66 2 x 2-block Cholesky jobs in the certified
+    pass, more than one 64-entry argument table of those kernels holds: the jobs go out in chunks."""
     import bench
     from ttutil import tt_diff_norm
 
@@ -365,6 +365,66 @@ def test_round_ranks_above_512(handle, ref, n, ranks):
     e_ref, _ = _tt_diff_norm(ref, y.cores, x.cores)
     e_gpu, _ = _tt_diff_norm(ref, g2.cores(), x.cores)
     assert abs(e_gpu - e_ref) <= 1e-6 * nrm
+
+
+def test_round_all_cholesky_size_classes(handle, ref):
+    """Ranks 30 / 600 / 300 / 30: one certified pass factors Grams of all three size classes (n <= 256
+    register-resident, 257..512 as 2 x 2 blocks, above 512 blocked) through one batched-Cholesky call.
+    Without a cut: the chain round, exact ranks, right-orthonormal cores, same tensor (the bars of
+    test_round_ranks_above_512); with one: the oracle's ranks and truncation error on the certified
+    truncating path. (Worst tr(G) / lambda_min over both Gram chains of this input, from the oracle's
+    cores: 1.4e5 left, 5.9e7 right -- three orders inside the certificate's limit 1 / kGramShift = 1e11.)"""
+    dims, ranks = [30] * 5, [30, 600, 300, 30]
+    x = ref.TT.random_raw(dims, ranks, ref.Rng(73))
+    g = capi.TTDevice.from_cores(handle, [c.copy() for c in x.cores])
+    g.round(600)
+    assert g.ranks == ranks
+    assert handle.last_round_path() == "chain"
+    gc = g.cores()
+    for c in gc[1:]:
+        M = c.reshape(c.shape[0], -1)
+        assert np.abs(M @ M.T - np.eye(M.shape[0])).max() <= 1e-12
+    diff, nrm = _tt_diff_norm(ref, gc, x.cores)
+    assert diff <= 1e-10 * nrm
+    g2 = capi.TTDevice.from_cores(handle, [c.copy() for c in x.cores])
+    g2.round(200)
+    y = x.copy()
+    y.round(200)
+    assert g2.ranks == y.ranks
+    assert handle.last_round_path() == "truncate"
+    e_ref, _ = _tt_diff_norm(ref, y.cores, x.cores)
+    e_gpu, _ = _tt_diff_norm(ref, g2.cores(), x.cores)
+    assert abs(e_gpu - e_ref) <= 1e-6 * nrm
+
+
+def test_round_more_small_jobs_than_one_table(handle, ref):
+    """Order 40, rank 3: the certified pass has 39 edges x 3 = 117 factorisations of n <= 256, more than
+    one 48-entry kernel table holds, and the truncating round's left pass 78: both go out in chunks.
+    (Worst tr(G) / lambda_min over both Gram chains: 1.7e2.)"""
+    d = 40
+    dims, ranks = [3] * d, [min(3, 3 ** min(k, d - k)) for k in range(1, d)]
+    x = ref.TT.random_raw(dims, ranks, ref.Rng(71))
+    g = capi.TTDevice.from_cores(handle, [c.copy() for c in x.cores])
+    g.round(3)
+    assert g.ranks == ranks
+    assert handle.last_round_path() == "chain"
+    gc = g.cores()
+    for c in gc[1:]:
+        M = c.reshape(c.shape[0], -1)
+        assert np.abs(M @ M.T - np.eye(M.shape[0])).max() <= 1e-12
+    diff, nrm = _tt_diff_norm(ref, gc, x.cores)
+    assert diff <= 1e-10 * nrm
+    g2 = capi.TTDevice.from_cores(handle, [c.copy() for c in x.cores])
+    g2.round(2)
+    y = x.copy()
+    y.round(2)
+    assert g2.ranks == y.ranks
+    e_ref, _ = _tt_diff_norm(ref, y.cores, x.cores)
+    e_gpu, _ = _tt_diff_norm(ref, g2.cores(), x.cores)
+    assert abs(e_gpu - e_ref) <= 1e-6 * nrm
+    for c in g2.cores()[1:]:   # right-canonical result
+        M = c.reshape(c.shape[0], -1)
+        assert np.abs(M @ M.T - np.eye(M.shape[0])).max() <= 1e-12
 
 
 @pytest.mark.parametrize("edge", [None, 1])

@@ -1,0 +1,290 @@
+// Batched Cholesky front end of the TT rounds (chol_batch.hpp): dispatch of a job list over the three size
+// classes -- n <= 256 (register-resident batched kernels, smallla.hip), 257..512 (2 x 2 blocks of those,
+// below) and above (blocked, solve.hip chol_full) -- with the kernels' argument tables chunked here.
+#include <algorithm>
+
+#include "tt_common.hpp"
+
+namespace xrs {
+
+namespace {
+
+using ttd::GemmJob;
+using ttd::gemm_grouped;
+
+static_assert(kCholLaunchJobs == kPotrfBatchMax);
+constexpr int kBigMax = 64;   // entries of the 2 x 2-block kernels' argument tables
+struct BigJob {
+    const double* src;
+    double shift_rel;
+    int n;
+    double* L;   // factor jobs: full L and Z = L^{-1} (n x n); certificates: both null
+    double* Z;
+};
+
+// ---- Cholesky for 256 < n <= 512 from the n <= 256 kernels (2 x 2 blocks, n1 = 256, n2 = n - 256):
+//   W = A + shift*I (shift = shift_rel tr A), L11 = chol(W11), Z11 = L11^{-1}, L21 = W21 Z11^T,
+//   L22 = chol(W22 - L21 L21^T); factor jobs also get L = [L11 0; L21 L22] and
+//   Z = L^{-1} = [Z11 0; -Z22 L21 Z11, Z22]. Every step is one batched launch over all jobs, so the
+//   latency is two 256-Cholesky + two 256-inverses instead of one 512-column sequential sweep
+//   (k_potrf32_batched + k_trinv_batched<32>: 1.1 ms per cfg5 pass).
+struct BigArgs {
+    const double* src[kBigMax];
+    double* w11[kBigMax];
+    double* w21[kBigMax];
+    double* w22[kBigMax];
+    double shift[kBigMax];
+    int n[kBigMax];
+};
+
+__global__ void __launch_bounds__(256) k_split_shift(const BigArgs a) {
+    const int j = blockIdx.y, n = a.n[j], n1 = 256, n2 = n - 256;
+    const double* A = a.src[j];
+    __shared__ double red[4];
+    double tr = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) tr += A[size_t(i) * n + i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) tr += __shfl_xor(tr, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = tr;
+    __syncthreads();
+    const double shift = a.shift[j] * (red[0] + red[1] + red[2] + red[3]);
+    const size_t total = size_t(n) * n;
+    for (size_t e = size_t(blockIdx.x) * 256 + threadIdx.x; e < total; e += size_t(gridDim.x) * 256) {
+        const int r = int(e / n), c = int(e - size_t(r) * n);
+        const double v = A[e] + (r == c ? shift : 0.0);
+        if (r < n1 && c < n1) a.w11[j][size_t(r) * n1 + c] = v;
+        else if (r >= n1 && c < n1) a.w21[j][size_t(r - n1) * n1 + c] = v;
+        else if (r >= n1 && c >= n1) a.w22[j][size_t(r - n1) * n2 + (c - n1)] = v;
+    }
+}
+
+struct SubArgs {
+    double* y[kBigMax];
+    const double* x[kBigMax];
+    int count[kBigMax];
+};
+
+__global__ void __launch_bounds__(256) k_sub_batched(const SubArgs a) {   // y -= x
+    const int j = blockIdx.y;
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < a.count[j]; e += gridDim.x * 256) a.y[j][e] -= a.x[j][e];
+}
+
+struct AssembleArgs {
+    double* out[kBigMax];   // n x n
+    const double* b11[kBigMax];
+    const double* b21[kBigMax];
+    const double* b22[kBigMax];
+    int n[kBigMax];
+};
+
+__global__ void __launch_bounds__(256) k_assemble_lower(const AssembleArgs a) {   // [B11 0; B21 B22]
+    const int j = blockIdx.y, n = a.n[j], n1 = 256, n2 = n - 256;
+    const size_t total = size_t(n) * n;
+    for (size_t e = size_t(blockIdx.x) * 256 + threadIdx.x; e < total; e += size_t(gridDim.x) * 256) {
+        const int r = int(e / n), c = int(e - size_t(r) * n);
+        double v = 0.0;
+        if (r < n1) v = c < n1 ? a.b11[j][size_t(r) * n1 + c] : 0.0;
+        else v = c < n1 ? a.b21[j][size_t(r - n1) * n1 + c] : a.b22[j][size_t(r - n1) * n2 + (c - n1)];
+        a.out[j][e] = v;
+    }
+}
+
+
+// Enqueues every job; statuses (2 per job: the two diagonal factorisations) go to status[0 .. 2*jobs).
+void factor_big(xrs_handle_t h, const std::vector<BigJob>& jobs, int* status, std::vector<DevBuf>& keep) {
+    const int nj = int(jobs.size());
+    XRS_REQUIRE(nj <= kBigMax, "factor_big: too many jobs");
+    constexpr int n1 = 256;
+    BigArgs ba{};
+    std::vector<double*> w11(nj), w21(nj), w22(nj), d11(nj), d22(nj), z11(nj), pp(nj);
+    auto buf = [&](size_t elems) { keep.emplace_back(h, std::max<size_t>(elems, 1) * 8); return keep.back().d(); };
+    size_t maxn2 = 0;
+    for (int j = 0; j < nj; ++j) {
+        const int n = jobs[j].n, n2 = n - n1;
+        XRS_REQUIRE(n > n1 && n <= 2 * n1, "factor_big: n out of range");
+        w11[j] = buf(size_t(n1) * n1);
+        w21[j] = buf(size_t(n2) * n1);
+        w22[j] = buf(size_t(n2) * n2);
+        d11[j] = buf(dinv_elems(n1));
+        d22[j] = buf(dinv_elems(n2));
+        z11[j] = buf(size_t(n1) * n1);
+        pp[j] = buf(size_t(n2) * n2);
+        ba.src[j] = jobs[j].src;
+        ba.w11[j] = w11[j];
+        ba.w21[j] = w21[j];
+        ba.w22[j] = w22[j];
+        ba.shift[j] = jobs[j].shift_rel;
+        ba.n[j] = n;
+        maxn2 = std::max(maxn2, size_t(n2));
+    }
+    hipLaunchKernelGGL(k_split_shift, dim3(256, nj), dim3(256), 0, h->stream, ba);
+    check_launch("k_split_shift");
+    auto chol = [&](const std::vector<double*>& W, const std::vector<double*>& D, int first_slot, bool upper_half) {
+        for (int b0 = 0; b0 < nj; b0 += kPotrfBatchMax) {
+            PotrfBatch pb{};
+            const int c = std::min(kPotrfBatchMax, nj - b0);
+            for (int i = 0; i < c; ++i) {
+                pb.src[i] = nullptr;
+                pb.G[i] = W[b0 + i];
+                pb.Dinv[i] = D[b0 + i];
+                pb.shift[i] = 0.0;
+                pb.n[i] = upper_half ? n1 : jobs[b0 + i].n - n1;
+            }
+            pb.status = status + first_slot + b0;
+            potrf_batched(h, pb, c);
+        }
+    };
+    auto inverse = [&](const std::vector<double*>& L, const std::vector<double*>& D, const std::vector<double*>& X,
+                       bool upper_half, const std::vector<int>& which) {
+        TrinvBatch tb{};
+        int c = 0;
+        for (int j : which) {
+            tb.L[c] = L[j];
+            tb.Dinv[c] = D[j];
+            tb.X[c] = X[j];
+            tb.n[c] = upper_half ? n1 : jobs[j].n - n1;
+            ++c;
+        }
+        if (c) trinv_batched(h, tb, c);
+    };
+    std::vector<int> all(nj), fac;
+    for (int j = 0; j < nj; ++j) {
+        all[j] = j;
+        if (jobs[j].L) fac.push_back(j);
+    }
+    chol(w11, d11, 0, true);                     // L11 in w11
+    inverse(w11, d11, z11, true, all);           // Z11
+    std::vector<GemmJob> g1, g2;
+    for (int j = 0; j < nj; ++j) {
+        const size_t n2 = size_t(jobs[j].n - n1);
+        g1.push_back({n2, size_t(n1), size_t(n1), size_t(n1), size_t(n1), false, true, w21[j], z11[j], w21[j] == nullptr ? nullptr : buf(n2 * n1)});
+    }
+    // L21 = W21 Z11^T into fresh buffers (GEMM outputs must not alias inputs)
+    std::vector<double*> l21(nj);
+    for (int j = 0; j < nj; ++j) l21[j] = g1[j].C;
+    gemm_grouped(h, g1);
+    for (int j = 0; j < nj; ++j) {
+        const size_t n2 = size_t(jobs[j].n - n1);
+        g2.push_back({n2, n2, size_t(n1), size_t(n1), size_t(n1), false, true, l21[j], l21[j], pp[j], true});
+    }
+    gemm_grouped(h, g2);                         // P = L21 L21^T (symmetric)
+    SubArgs sa{};
+    for (int j = 0; j < nj; ++j) {
+        sa.y[j] = w22[j];
+        sa.x[j] = pp[j];
+        sa.count[j] = (jobs[j].n - n1) * (jobs[j].n - n1);
+    }
+    hipLaunchKernelGGL(k_sub_batched, dim3(64, nj), dim3(256), 0, h->stream, sa);
+    check_launch("k_sub_batched");
+    chol(w22, d22, nj, false);                   // L22 in w22
+    if (fac.empty()) return;
+    std::vector<double*> z22(nj, nullptr), tt(nj, nullptr), z21(nj, nullptr);
+    for (int j : fac) {
+        const size_t n2 = size_t(jobs[j].n - n1);
+        z22[j] = buf(n2 * n2);
+        tt[j] = buf(n2 * n1);
+        z21[j] = buf(n2 * n1);
+    }
+    inverse(w22, d22, z22, false, fac);          // Z22
+    std::vector<GemmJob> g3, g4;
+    for (int j : fac) {
+        const size_t n2 = size_t(jobs[j].n - n1);
+        g3.push_back({n2, size_t(n1), size_t(n1), size_t(n1), size_t(n1), false, false, l21[j], z11[j], tt[j]});
+    }
+    gemm_grouped(h, g3);                         // T = L21 Z11
+    for (int j : fac) {
+        const size_t n2 = size_t(jobs[j].n - n1);
+        GemmJob g{n2, size_t(n1), n2, n2, size_t(n1), false, false, z22[j], tt[j], z21[j]};
+        g.alpha = -1.0;
+        g4.push_back(g);
+    }
+    gemm_grouped(h, g4);                         // Z21 = -Z22 T
+    AssembleArgs al{}, az{};
+    int c = 0;
+    for (int j : fac) {
+        al.out[c] = jobs[j].L; al.b11[c] = w11[j]; al.b21[c] = l21[j]; al.b22[c] = w22[j]; al.n[c] = jobs[j].n;
+        az.out[c] = jobs[j].Z; az.b11[c] = z11[j]; az.b21[c] = z21[j]; az.b22[c] = z22[j]; az.n[c] = jobs[j].n;
+        ++c;
+    }
+    hipLaunchKernelGGL(k_assemble_lower, dim3(256, c), dim3(256), 0, h->stream, al);
+    check_launch("k_assemble_lower");
+    hipLaunchKernelGGL(k_assemble_lower, dim3(256, c), dim3(256), 0, h->stream, az);
+    check_launch("k_assemble_lower");
+}
+
+}  // namespace
+
+int chol_status_count(const std::vector<CholJob>& jobs) {
+    int c = 0;
+    for (const CholJob& j : jobs) c += j.n > 512 ? chol_full_blocks(size_t(j.n)) : (j.n > 256 ? 2 : 1);
+    return c;
+}
+
+// Status layout: one word per n <= 256 job in job order, then two per 257..512 job, then the blocks of the
+// larger ones.
+void chol_enqueue(xrs_handle_t h, const std::vector<CholJob>& jobs, int* status, std::vector<DevBuf>& keep) {
+    std::vector<const CholJob*> small, huge;
+    std::vector<BigJob> big;
+    size_t dsz = 0;
+    for (const CholJob& j : jobs) {
+        XRS_REQUIRE(j.A != nullptr && j.n >= 1, "chol_enqueue: empty job");
+        if (j.n > 512) {
+            huge.push_back(&j);
+        } else if (j.n > 256) {
+            double* Z = j.Z;   // (the 2 x 2 blocks always build L^{-1} beside L)
+            if (j.L && !Z) {
+                keep.emplace_back(h, size_t(j.n) * j.n * 8);
+                Z = keep.back().d();
+            }
+            big.push_back({j.A, j.shift, j.n, j.L, Z});
+        } else {
+            small.push_back(&j);
+            dsz += dinv_elems(j.n);
+        }
+    }
+    const int ns = int(small.size());
+    int slot = ns + 2 * int(big.size());
+    for (const CholJob* j : huge) {
+        chol_full(h, j->A, size_t(j->n), j->shift, j->L, j->Z, status + slot);
+        slot += chol_full_blocks(size_t(j->n));
+    }
+    for (size_t b0 = 0; b0 < big.size(); b0 += kBigMax) {
+        const std::vector<BigJob> part(big.begin() + long(b0), big.begin() + long(std::min(big.size(), b0 + kBigMax)));
+        factor_big(h, part, status + ns + 2 * b0, keep);
+    }
+    if (ns == 0) return;
+    keep.emplace_back(h, dsz * 8);   // the diagonal-block inverses of every n <= 256 job: one slab per call
+    double* dinv = keep.back().d();
+    struct Inverse { const double* L; const double* Dinv; double* X; int n; };
+    std::vector<Inverse> inv;   // the factor jobs that ask for Z
+    for (int b0 = 0; b0 < ns; b0 += kPotrfBatchMax) {
+        PotrfBatch pb{};
+        const int c = std::min(kPotrfBatchMax, ns - b0);
+        for (int i = 0; i < c; ++i) {
+            const CholJob& j = *small[size_t(b0 + i)];
+            pb.src[i] = j.A;
+            pb.G[i] = j.L;
+            pb.Dinv[i] = dinv;
+            pb.shift[i] = j.shift;
+            pb.n[i] = j.n;
+            if (j.L && j.Z) inv.push_back({j.L, dinv, j.Z, j.n});
+            dinv += dinv_elems(j.n);
+        }
+        pb.status = status + b0;
+        potrf_batched(h, pb, c);
+    }
+    for (size_t b0 = 0; b0 < inv.size(); b0 += kTrinvBatchMax) {
+        TrinvBatch tb{};
+        const int c = int(std::min<size_t>(kTrinvBatchMax, inv.size() - b0));
+        for (int i = 0; i < c; ++i) {
+            const Inverse& v = inv[b0 + size_t(i)];
+            tb.L[i] = v.L;
+            tb.Dinv[i] = v.Dinv;
+            tb.X[i] = v.X;
+            tb.n[i] = v.n;
+        }
+        trinv_batched(h, tb, c);
+    }
+}
+
+}  // namespace xrs

@@ -23,6 +23,7 @@
 #include <cstring>
 
 #include "runtime.hpp"
+#include "scratch_map.hpp"
 #include "sgemm.hpp"
 #include "tt_internal.hpp"
 
@@ -263,9 +264,9 @@ double dot_f32(xrs_handle_t h, size_t d, const size_t* n, const size_t* rx, cons
     }
     dot32_enqueue(h, d, n, rx, X, ry, Y, b, st);
     // read back the closing sum, the core maxima and the max words' values (+ the front end's exponent words)
-    char* hs = static_cast<char*>(h->host_scratch);
+    char* hs = static_cast<char*>(h->host_scratch);   // (the whole area: no other user is live beside a zipper)
     const size_t zoff = (b.back_bytes + 255) / 256 * 256;
-    XRS_REQUIRE(zoff + 16 * d <= (size_t(1) << 16), "fp32 zipper: read-back exceeds the host scratch");
+    XRS_REQUIRE(zoff + 16 * d <= scratch::kBytes, "fp32 zipper: read-back exceeds the host scratch");
     XRS_HIP(hipMemcpyAsync(hs, b.W, b.back_bytes, hipMemcpyDeviceToHost, h->stream));
     if (use_front) XRS_HIP(hipMemcpyAsync(hs + zoff, fr.words, 16 * d, hipMemcpyDeviceToHost, h->stream));
     host_wait(h);

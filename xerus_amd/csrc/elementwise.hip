@@ -6,6 +6,7 @@
 #include <cmath>
 
 #include "elementwise.hpp"
+#include "scratch_map.hpp"
 
 namespace xrs {
 
@@ -120,8 +121,8 @@ __global__ void __launch_bounds__(RB) k_reduce_final(const double* __restrict__ 
 void reduce_to_device(xrs_handle_t h, int mode, const double* x, const double* y, size_t n, double* out_dev,
                       double* partial) {
     KernelTimer timer(h, XRS_KFAM_ELEMWISE, 2.0 * double(n), double(mode == 1 ? 2 : 1) * 8.0 * double(n));
-    if (partial == nullptr) partial = static_cast<double*>(h->dev_scratch) + 64;
     const int nb = int(std::max<size_t>(1, std::min<size_t>(RMAXB, (n + RB * 4 - 1) / (RB * 4))));
+    if (partial == nullptr) partial = scratch::dev<double>(h, scratch::kDevPartials, size_t(mode == 0 ? 3 : 1) * size_t(nb));
     if (mode == 0) hipLaunchKernelGGL(k_reduce_partial<0>, dim3(nb), dim3(RB), 0, h->stream, x, y, n, partial);
     else if (mode == 1) hipLaunchKernelGGL(k_reduce_partial<1>, dim3(nb), dim3(RB), 0, h->stream, x, y, n, partial);
     else hipLaunchKernelGGL(k_reduce_partial<2>, dim3(nb), dim3(RB), 0, h->stream, x, y, n, partial);
@@ -132,9 +133,9 @@ void reduce_to_device(xrs_handle_t h, int mode, const double* x, const double* y
 
 double reduce_to_host(xrs_handle_t h, int mode, const double* x, const double* y, size_t n) {
     if (n == 0) return 0.0;
-    double* out = static_cast<double*>(h->dev_scratch);
+    double* out = scratch::dev<double>(h, scratch::kDevResult);
     reduce_to_device(h, mode, x, y, n, out);
-    double* host = static_cast<double*>(h->host_scratch);
+    double* host = scratch::host<double>(h, scratch::kHostResult);
     XRS_HIP(hipMemcpyAsync(host, out, 8, hipMemcpyDeviceToHost, h->stream));
     host_wait(h);
     return host[0];
@@ -265,8 +266,8 @@ int range_exponent(double am) {
 
 int range_exponent(xrs_handle_t h, const double* A, size_t n) {
     if (!n) return 0;
-    double* am_dev = static_cast<double*>(h->dev_scratch) + 48;
-    double* am_host = static_cast<double*>(h->host_scratch) + 48;
+    double* am_dev = scratch::dev<double>(h, scratch::kDevAmax);
+    double* am_host = scratch::host<double>(h, scratch::kHostAmax);
     amax_enqueue(h, &A, &n, 1, am_dev);
     XRS_HIP(hipMemcpyAsync(am_host, am_dev, 8, hipMemcpyDeviceToHost, h->stream));
     XRS_HIP(hipStreamSynchronize(h->stream));

@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "scratch_map.hpp"
 #include "smallla.hpp"
 
 namespace xrs {
@@ -29,7 +30,7 @@ void transpose(xrs_handle_t h, double* out, const double* in, size_t rows, size_
 }
 
 int read_status(xrs_handle_t h, const int* status_dev, int count, int* host_out) {
-    int* hs = static_cast<int*>(h->host_scratch);
+    int* hs = scratch::host<int>(h, scratch::kHostLocal, size_t(count));
     XRS_HIP(hipMemcpyAsync(hs, status_dev, size_t(count) * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     XRS_HIP(hipStreamSynchronize(h->stream));
     int any = 0;
@@ -91,10 +92,10 @@ __global__ void __launch_bounds__(256) k_first_order(const double* __restrict__ 
 }
 
 static double max_abs_dev_identity(xrs_handle_t h, const double* G, size_t n) {
-    double* out = static_cast<double*>(h->dev_scratch) + 32;
+    double* out = scratch::dev<double>(h, scratch::kDevIdentityDev);
     hipLaunchKernelGGL(k_dev_identity, dim3(1), dim3(256), 0, h->stream, G, int(n), out);
     check_launch("k_dev_identity");
-    double* hs = static_cast<double*>(h->host_scratch) + 32;
+    double* hs = scratch::host<double>(h, scratch::kHostIdentityDev);
     XRS_HIP(hipMemcpyAsync(hs, out, 8, hipMemcpyDeviceToHost, h->stream));
     XRS_HIP(hipStreamSynchronize(h->stream));
     const double v = hs[0];
@@ -195,12 +196,12 @@ OrthResult orthogonalize(xrs_handle_t h, const double* A, size_t m, size_t n, bo
         // second pass: first-order correction when Q1 is already orthonormal to ~1e-8 (then the
         // neglected O(E^2) term is below u), else a full second Cholesky + TRSM
         DevBuf L2(h, N * N * 8), Li2(h, N * N * 8);
-        double* emax_dev = static_cast<double*>(h->dev_scratch) + 40;
         const unsigned nb = 8;
+        double* emax_dev = scratch::dev<double>(h, scratch::kDevOrthEmax, nb);
         hipLaunchKernelGGL(k_first_order, dim3(nb), dim3(256), 0, h->stream, L1.d(), Ni, L2.d(), Li2.d(), emax_dev);
         check_launch("k_first_order");
-        int* hs = static_cast<int*>(h->host_scratch);
-        double* hd = static_cast<double*>(h->host_scratch) + 8;
+        int* hs = scratch::host<int>(h, scratch::kHostResult, 2);
+        double* hd = scratch::host<double>(h, scratch::kHostOrthEmax, nb);
         XRS_HIP(hipMemcpyAsync(hs, stv, 8, hipMemcpyDeviceToHost, h->stream));
         XRS_HIP(hipMemcpyAsync(hd, emax_dev, nb * 8, hipMemcpyDeviceToHost, h->stream));
         XRS_HIP(hipStreamSynchronize(h->stream));
@@ -365,8 +366,8 @@ static void rq_core(xrs_handle_t h, const double* A, size_t m, size_t n, double*
 // holds no iterative kernel (bounded column loops) and whose result is discarded, is factorised a second time.
 template <class Run, class Back>
 static auto range_controlled(xrs_handle_t h, const double* A, size_t count, Run run, Back scale_back) {
-    double* am_dev = static_cast<double*>(h->dev_scratch) + 49;
-    double* am_host = static_cast<double*>(h->host_scratch) + 49;
+    double* am_dev = scratch::dev<double>(h, scratch::kDevRangeAmax);
+    double* am_host = scratch::host<double>(h, scratch::kHostRangeAmax);
     amax_enqueue(h, &A, &count, 1, am_dev);
     XRS_HIP(hipMemcpyAsync(am_host, am_dev, 8, hipMemcpyDeviceToHost, h->stream));
     auto exponent = [&] { return range_exponent(am_host[0]); };

@@ -1,5 +1,6 @@
 // Handle, stream, caching allocator, profiler and the runtime part of the C-ABI.
 #include "runtime.hpp"
+#include "scratch_map.hpp"
 
 #include <algorithm>
 
@@ -252,8 +253,8 @@ static void init_handle_resources(xrs_handle_t h) {
         XRS_HIP(hipEventCreateWithFlags(&h->ev_aux, hipEventDisableTiming));
         XRS_HIP(hipEventCreateWithFlags(&h->ev_dot, hipEventDisableTiming));
         XRS_HIP(hipEventCreateWithFlags(&h->ev_dot_join, hipEventDisableTiming));
-        XRS_HIP(hipHostMalloc(&h->host_scratch, 1 << 16, hipHostMallocDefault));
-        XRS_HIP(hipMalloc(&h->dev_scratch, 1 << 16));
+        XRS_HIP(hipHostMalloc(&h->host_scratch, scratch::kBytes, hipHostMallocDefault));
+        XRS_HIP(hipMalloc(&h->dev_scratch, scratch::kBytes));
         const size_t tbytes = size_t(1 + xrs_handle_s::kSides) * xrs_handle_s::kTicketCap * sizeof(int);
         XRS_HIP(hipMalloc(&h->ticket_base, tbytes));
         XRS_HIP(hipMemset(h->ticket_base, 0, tbytes));

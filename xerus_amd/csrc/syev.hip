@@ -34,6 +34,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "scratch_map.hpp"
 #include "smallla.hpp"
 
 namespace xrs {
@@ -1474,7 +1475,7 @@ bool svd_bidiag(xrs_handle_t h, const double* A, int n, double* U, double* S, do
     }
     hipLaunchKernelGGL(k_svd_check, dim3(1), dim3(1024), 0, h->stream, Vb, A, Z.d(), Z.d() + nn, n, chk.d());
     check_launch("k_svd_check");
-    double* hc = static_cast<double*>(h->host_scratch) + 80;   // (pinned; a slot of its own)
+    double* hc = scratch::host<double>(h, scratch::kHostSvdCheck, 5);
     XRS_HIP(hipMemcpyAsync(hc, chk.d(), 32, hipMemcpyDeviceToHost, h->stream));
     XRS_HIP(hipMemcpyAsync(hc + 4, st.d(), 4, hipMemcpyDeviceToHost, h->stream));
     XRS_HIP(hipStreamSynchronize(h->stream));

@@ -365,6 +365,7 @@ void project(xrs_handle_t h, size_t d, const size_t* n, const size_t* ru, const 
                 right_step(d - 1 - s);
             }
             fork.side(1);   // every factorisation, behind the UU chain
+            // (not through chol_enqueue: 257..512 goes to the 32-block kernel here, with k_tangent_cert in between)
             for (size_t e0 = 0; e0 < E; e0 += kSegMax) {
                 const int cnt = int(std::min<size_t>(kSegMax, E - e0));
                 PotrfBatch pb{};
@@ -531,7 +532,7 @@ double tangent_dot(xrs_handle_t h, size_t d, const size_t* n, const size_t* r, c
         hipLaunchKernelGGL(k_tangent_dot, dim3(std::min(chunks, kBlocksMax)), dim3(256), 0, h->stream, a);
         check_launch("k_tangent_dot");
     }
-    double* hs = static_cast<double*>(h->host_scratch);
+    double* hs = scratch::host<double>(h, scratch::kHostLocal, launches);
     XRS_HIP(hipMemcpyAsync(hs, res.d(), launches * 8, hipMemcpyDeviceToHost, h->stream));
     host_wait(h);
     double sum = 0.0;

@@ -344,16 +344,7 @@ __global__ void __launch_bounds__(256) k_dev_identity_many(const DevIdArgs args)
 void rl_sweep(TT& t, const size_t* max_ranks, double eps, double cX, size_t from);
 
 
-// One chain orthogonalisation pass over the current cores: the right Gram chain H_k (and, with
-// `certify`, the left chain G_k), ONE batched launch of all Cholesky factorisations -- H_k = L_k L_k^T
-// (out of place, into L_k) and, with `certify`, the down-shifted certificates of G_k and H_k (status
-// only) -- then every core is transformed independently: C_k = L_k^{-1} M_k (I (x) L_{k+1}),
-// C_0 = M_0 (I (x) L_1). In exact arithmetic the C_k (k >= 1) have orthonormal rows and represent the
-// same tensor. Nothing is synchronised: the factorisation statuses are copied to pinned host memory
-// behind the transforms and judged by chain_check (a failed factorisation only makes C garbage, which
-// is then discarded).
 // Independent GEMMs; the ones of identical shape go out as one batched launch.
-
 void gemm_grouped(xrs_handle_t h, const std::vector<GemmJob>& jobs) {
     std::vector<bool> done(jobs.size(), false);
     for (size_t i = 0; i < jobs.size(); ++i) {
@@ -378,316 +369,60 @@ void gemm_grouped(xrs_handle_t h, const std::vector<GemmJob>& jobs) {
     }
 }
 
-// ---- Cholesky for 256 < n <= 512 from the n <= 256 kernels (2 x 2 blocks, n1 = 256, n2 = n - 256):
-//   W = A + shift*I (shift = shift_rel tr A), L11 = chol(W11), Z11 = L11^{-1}, L21 = W21 Z11^T,
-//   L22 = chol(W22 - L21 L21^T); factor jobs also get L = [L11 0; L21 L22] and
-//   Z = L^{-1} = [Z11 0; -Z22 L21 Z11, Z22]. Every step is one batched launch over all jobs, so the
-//   latency is two 256-Cholesky + two 256-inverses instead of one 512-column sequential sweep
-//   (k_potrf32_batched + k_trinv_batched<32>: 1.1 ms per cfg5 pass).
-struct BigArgs {
-    const double* src[kBigMax];
-    double* w11[kBigMax];
-    double* w21[kBigMax];
-    double* w22[kBigMax];
-    double shift[kBigMax];
-    int n[kBigMax];
-};
-
-__global__ void __launch_bounds__(256) k_split_shift(const BigArgs a) {
-    const int j = blockIdx.y, n = a.n[j], n1 = 256, n2 = n - 256;
-    const double* A = a.src[j];
-    __shared__ double red[4];
-    double tr = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) tr += A[size_t(i) * n + i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) tr += __shfl_xor(tr, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = tr;
-    __syncthreads();
-    const double shift = a.shift[j] * (red[0] + red[1] + red[2] + red[3]);
-    const size_t total = size_t(n) * n;
-    for (size_t e = size_t(blockIdx.x) * 256 + threadIdx.x; e < total; e += size_t(gridDim.x) * 256) {
-        const int r = int(e / n), c = int(e - size_t(r) * n);
-        const double v = A[e] + (r == c ? shift : 0.0);
-        if (r < n1 && c < n1) a.w11[j][size_t(r) * n1 + c] = v;
-        else if (r >= n1 && c < n1) a.w21[j][size_t(r - n1) * n1 + c] = v;
-        else if (r >= n1 && c >= n1) a.w22[j][size_t(r - n1) * n2 + (c - n1)] = v;
-    }
-}
-
-struct SubArgs {
-    double* y[kBigMax];
-    const double* x[kBigMax];
-    int count[kBigMax];
-};
-
-__global__ void __launch_bounds__(256) k_sub_batched(const SubArgs a) {   // y -= x
-    const int j = blockIdx.y;
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < a.count[j]; e += gridDim.x * 256) a.y[j][e] -= a.x[j][e];
-}
-
-struct AssembleArgs {
-    double* out[kBigMax];   // n x n
-    const double* b11[kBigMax];
-    const double* b21[kBigMax];
-    const double* b22[kBigMax];
-    int n[kBigMax];
-};
-
-__global__ void __launch_bounds__(256) k_assemble_lower(const AssembleArgs a) {   // [B11 0; B21 B22]
-    const int j = blockIdx.y, n = a.n[j], n1 = 256, n2 = n - 256;
-    const size_t total = size_t(n) * n;
-    for (size_t e = size_t(blockIdx.x) * 256 + threadIdx.x; e < total; e += size_t(gridDim.x) * 256) {
-        const int r = int(e / n), c = int(e - size_t(r) * n);
-        double v = 0.0;
-        if (r < n1) v = c < n1 ? a.b11[j][size_t(r) * n1 + c] : 0.0;
-        else v = c < n1 ? a.b21[j][size_t(r - n1) * n1 + c] : a.b22[j][size_t(r - n1) * n2 + (c - n1)];
-        a.out[j][e] = v;
-    }
-}
-
-
-// Enqueues every job; statuses (2 per job: the two diagonal factorisations) go to status[0 .. 2*jobs).
-void factor_big(xrs_handle_t h, const std::vector<BigJob>& jobs, int* status, std::vector<DevBuf>& keep) {
-    const int nj = int(jobs.size());
-    XRS_REQUIRE(nj <= kBigMax, "factor_big: too many jobs");
-    constexpr int n1 = 256;
-    BigArgs ba{};
-    std::vector<double*> w11(nj), w21(nj), w22(nj), d11(nj), d22(nj), z11(nj), pp(nj);
-    auto buf = [&](size_t elems) { keep.emplace_back(h, std::max<size_t>(elems, 1) * 8); return keep.back().d(); };
-    size_t maxn2 = 0;
-    for (int j = 0; j < nj; ++j) {
-        const int n = jobs[j].n, n2 = n - n1;
-        XRS_REQUIRE(n > n1 && n <= 2 * n1, "factor_big: n out of range");
-        w11[j] = buf(size_t(n1) * n1);
-        w21[j] = buf(size_t(n2) * n1);
-        w22[j] = buf(size_t(n2) * n2);
-        d11[j] = buf(dinv_elems(n1));
-        d22[j] = buf(dinv_elems(n2));
-        z11[j] = buf(size_t(n1) * n1);
-        pp[j] = buf(size_t(n2) * n2);
-        ba.src[j] = jobs[j].src;
-        ba.w11[j] = w11[j];
-        ba.w21[j] = w21[j];
-        ba.w22[j] = w22[j];
-        ba.shift[j] = jobs[j].shift_rel;
-        ba.n[j] = n;
-        maxn2 = std::max(maxn2, size_t(n2));
-    }
-    hipLaunchKernelGGL(k_split_shift, dim3(256, nj), dim3(256), 0, h->stream, ba);
-    check_launch("k_split_shift");
-    auto chol = [&](const std::vector<double*>& W, const std::vector<double*>& D, int first_slot, bool upper_half) {
-        for (int b0 = 0; b0 < nj; b0 += kPotrfBatchMax) {
-            PotrfBatch pb{};
-            const int c = std::min(kPotrfBatchMax, nj - b0);
-            for (int i = 0; i < c; ++i) {
-                pb.src[i] = nullptr;
-                pb.G[i] = W[b0 + i];
-                pb.Dinv[i] = D[b0 + i];
-                pb.shift[i] = 0.0;
-                pb.n[i] = upper_half ? n1 : jobs[b0 + i].n - n1;
-            }
-            pb.status = status + first_slot + b0;
-            potrf_batched(h, pb, c);
-        }
-    };
-    auto inverse = [&](const std::vector<double*>& L, const std::vector<double*>& D, const std::vector<double*>& X,
-                       bool upper_half, const std::vector<int>& which) {
-        TrinvBatch tb{};
-        int c = 0;
-        for (int j : which) {
-            tb.L[c] = L[j];
-            tb.Dinv[c] = D[j];
-            tb.X[c] = X[j];
-            tb.n[c] = upper_half ? n1 : jobs[j].n - n1;
-            ++c;
-        }
-        if (c) trinv_batched(h, tb, c);
-    };
-    std::vector<int> all(nj), fac;
-    for (int j = 0; j < nj; ++j) {
-        all[j] = j;
-        if (jobs[j].L) fac.push_back(j);
-    }
-    chol(w11, d11, 0, true);                     // L11 in w11
-    inverse(w11, d11, z11, true, all);           // Z11
-    std::vector<GemmJob> g1, g2;
-    for (int j = 0; j < nj; ++j) {
-        const size_t n2 = size_t(jobs[j].n - n1);
-        g1.push_back({n2, size_t(n1), size_t(n1), size_t(n1), size_t(n1), false, true, w21[j], z11[j], w21[j] == nullptr ? nullptr : buf(n2 * n1)});
-    }
-    // L21 = W21 Z11^T into fresh buffers (GEMM outputs must not alias inputs)
-    std::vector<double*> l21(nj);
-    for (int j = 0; j < nj; ++j) l21[j] = g1[j].C;
-    gemm_grouped(h, g1);
-    for (int j = 0; j < nj; ++j) {
-        const size_t n2 = size_t(jobs[j].n - n1);
-        g2.push_back({n2, n2, size_t(n1), size_t(n1), size_t(n1), false, true, l21[j], l21[j], pp[j], true});
-    }
-    gemm_grouped(h, g2);                         // P = L21 L21^T (symmetric)
-    SubArgs sa{};
-    for (int j = 0; j < nj; ++j) {
-        sa.y[j] = w22[j];
-        sa.x[j] = pp[j];
-        sa.count[j] = (jobs[j].n - n1) * (jobs[j].n - n1);
-    }
-    hipLaunchKernelGGL(k_sub_batched, dim3(64, nj), dim3(256), 0, h->stream, sa);
-    check_launch("k_sub_batched");
-    chol(w22, d22, nj, false);                   // L22 in w22
-    if (fac.empty()) return;
-    std::vector<double*> z22(nj, nullptr), tt(nj, nullptr), z21(nj, nullptr);
-    for (int j : fac) {
-        const size_t n2 = size_t(jobs[j].n - n1);
-        z22[j] = buf(n2 * n2);
-        tt[j] = buf(n2 * n1);
-        z21[j] = buf(n2 * n1);
-    }
-    inverse(w22, d22, z22, false, fac);          // Z22
-    std::vector<GemmJob> g3, g4;
-    for (int j : fac) {
-        const size_t n2 = size_t(jobs[j].n - n1);
-        g3.push_back({n2, size_t(n1), size_t(n1), size_t(n1), size_t(n1), false, false, l21[j], z11[j], tt[j]});
-    }
-    gemm_grouped(h, g3);                         // T = L21 Z11
-    for (int j : fac) {
-        const size_t n2 = size_t(jobs[j].n - n1);
-        GemmJob g{n2, size_t(n1), n2, n2, size_t(n1), false, false, z22[j], tt[j], z21[j]};
-        g.alpha = -1.0;
-        g4.push_back(g);
-    }
-    gemm_grouped(h, g4);                         // Z21 = -Z22 T
-    AssembleArgs al{}, az{};
-    int c = 0;
-    for (int j : fac) {
-        al.out[c] = jobs[j].L; al.b11[c] = w11[j]; al.b21[c] = l21[j]; al.b22[c] = w22[j]; al.n[c] = jobs[j].n;
-        az.out[c] = jobs[j].Z; az.b11[c] = z11[j]; az.b21[c] = z21[j]; az.b22[c] = z22[j]; az.n[c] = jobs[j].n;
-        ++c;
-    }
-    hipLaunchKernelGGL(k_assemble_lower, dim3(256, c), dim3(256), 0, h->stream, al);
-    check_launch("k_assemble_lower");
-    hipLaunchKernelGGL(k_assemble_lower, dim3(256, c), dim3(256), 0, h->stream, az);
-    check_launch("k_assemble_lower");
-}
-
 struct ChainPass {
     std::vector<double*> C;   // new cores (owned by the TT's pool until replaced / released)
     int* status = nullptr;    // pinned host copy of the factorisation statuses
     int count = 0;
-    bool certify = false;
 };
 
-void chain_pass(TT& t, bool certify, ChainPass& out, int* host_status) {
+// One chain orthogonalisation pass over the current cores: the right Gram chain H_k (and, with
+// `certify`, the left chain G_k), ONE batched launch of all Cholesky factorisations -- H_k = L_k L_k^T
+// (out of place, into L_k) and, with `certify`, the down-shifted certificates of G_k and H_k (status
+// only) -- then every core is transformed independently: C_k = L_k^{-1} M_k (I (x) L_{k+1}),
+// C_0 = M_0 (I (x) L_1). In exact arithmetic the C_k (k >= 1) have orthonormal rows and represent the
+// same tensor. Nothing is synchronised: the factorisation statuses are copied to pinned host memory
+// behind the transforms and judged by chain_check (a failed factorisation only makes C garbage, which
+// is then discarded).
+void chain_pass(TT& t, bool certify, ChainPass& out) {
     const size_t d = t.d;
     xrs_handle_t h = t.h;
     std::vector<double*> G, H;
-    std::vector<DevBuf> gram_store, Lf(d), Cs;
+    std::vector<DevBuf> gram_store, Lf(d);
     XRS_MARK("pass");
     gram_chains(t, G, H, gram_store, certify);
     open_dot_gate(h);   // a gated async <x,y> runs beside the factorisations and transforms below
     XRS_MARK("chains");
-    // edges with r <= 256: one batched register-resident launch; larger (<= 512): factor_big (2 x 2
-    // blocks of the same kernels), which also delivers Z = L^{-1}
-    std::vector<DevBuf> Z(d);
+    // every factorisation of the pass through one front-end call (chol_batch.hpp): per edge H_k = L_k L_k^T with
+    // Z_k = L_k^{-1}, and with `certify` the status-only certificates of G_k and H_k
+    std::vector<DevBuf> Z(d), Cs;
     for (size_t k = 1; k < d; ++k) Z[k] = DevBuf(h, t.r[k] * t.r[k] * 8);
-    size_t dsz = 0;
-    for (size_t k = 1; k < d; ++k)
-        if (t.r[k] <= 256) dsz += dinv_elems(int(t.r[k]));
-    std::vector<double*> dinv(d, nullptr);
-    struct Job { const double* src; double* G; double* Dinv; double shift; int n; };
-    std::vector<Job> jobs;
-    std::vector<BigJob> big, huge;   // huge: r > 512, blocked Cholesky one job at a time
-    DevBuf Dv(h, dsz * 8 + 8), Dscr(h, (certify ? 2 * dsz : 1) * 8 + 8);
-    size_t off = 0;
+    std::vector<CholJob> jobs;
     for (size_t k = 1; k < d; ++k) {
         const size_t a = t.r[k];
         Lf[k] = DevBuf(h, a * a * 8);
-        if (a > 512) {
-            huge.push_back({H[k], 0.0, int(a), Lf[k].d(), Z[k].d()});
-            if (certify) {
-                huge.push_back({G[k], -kGramShift, int(a), nullptr, nullptr});
-                huge.push_back({H[k], -kGramShift, int(a), nullptr, nullptr});
-            }
-            continue;
+        jobs.push_back({H[k], int(a), Lf[k].d(), Z[k].d()});
+        if (certify) {
+            jobs.push_back(CholJob::certificate(G[k], int(a), kGramShift));
+            jobs.push_back(CholJob::certificate(H[k], int(a), kGramShift));
         }
-        if (a > 256) {
-            big.push_back({H[k], 0.0, int(a), Lf[k].d(), Z[k].d()});
-            if (certify) {
-                big.push_back({G[k], -kGramShift, int(a), nullptr, nullptr});
-                big.push_back({H[k], -kGramShift, int(a), nullptr, nullptr});
-            }
-            continue;
-        }
-        const size_t de = dinv_elems(int(a));
-        dinv[k] = Dv.d() + off;
-        jobs.push_back({H[k], Lf[k].d(), dinv[k], 0.0, int(a)});
-        if (certify) {   // status-only certificates
-            jobs.push_back({G[k], nullptr, Dscr.d() + 2 * off, -kGramShift, int(a)});
-            jobs.push_back({H[k], nullptr, Dscr.d() + 2 * off + de, -kGramShift, int(a)});
-        }
-        off += de;
     }
-    const int cnt_small = int(jobs.size());
-    int cnt_huge = 0;
-    for (const BigJob& j : huge) cnt_huge += chol_full_blocks(size_t(j.n));
-    const int cnt = cnt_small + 2 * int(big.size()) + cnt_huge;
+    const int cnt = chol_status_count(jobs);
+    int* host_status = scratch::host<int>(h, scratch::kHostChainStatus, size_t(cnt));
     DevBuf st(h, size_t(cnt) * 4 + 64);
-    {
-        int slot = cnt_small + 2 * int(big.size());
-        for (const BigJob& j : huge) {
-            chol_full(h, j.src, size_t(j.n), j.shift_rel, j.L, j.Z, st.as<int>() + slot);
-            slot += chol_full_blocks(size_t(j.n));
-        }
-    }
-    for (size_t b0 = 0; b0 < big.size(); b0 += kBigMax) {   // chunks of the kernels' argument tables
-        const std::vector<BigJob> part(big.begin() + long(b0), big.begin() + long(std::min(big.size(), b0 + kBigMax)));
-        factor_big(h, part, st.as<int>() + cnt_small + 2 * b0, Cs);
-    }
-    for (int b0 = 0; b0 < cnt_small; b0 += kPotrfBatchMax) {
-        PotrfBatch pb{};
-        const int c = std::min(kPotrfBatchMax, cnt_small - b0);
-        for (int i = 0; i < c; ++i) {
-            pb.src[i] = jobs[b0 + i].src;
-            pb.G[i] = jobs[b0 + i].G;
-            pb.Dinv[i] = jobs[b0 + i].Dinv;
-            pb.shift[i] = jobs[b0 + i].shift;
-            pb.n[i] = jobs[b0 + i].n;
-        }
-        pb.status = st.as<int>() + b0;
-        potrf_batched(h, pb, c);
-    }
+    chol_enqueue(h, jobs, st.as<int>(), Cs);
     XRS_HIP(hipMemcpyAsync(host_status, st.d(), size_t(cnt) * 4, hipMemcpyDeviceToHost, h->stream));
     XRS_MARK("potrf");
     out.status = host_status;
     out.count = cnt;
-    out.certify = certify;
     // The d transforms are independent: same-shape GEMMs go out as one batched launch each, all on the
     // main stream (cross-stream event hops cost ~20 us each here; a batch fills the chip as well as
     // concurrent streams do). The left factor is applied as a GEMM with the explicit inverse
     // Z_k = L_k^{-1} (one batched launch); the check below certifies the result either way.
     out.C.assign(d, nullptr);
     std::vector<DevBuf> W(d);
-    TrinvBatch tb{};
-    int ninv = 0;
     for (size_t k = 0; k < d; ++k) {
         out.C[k] = t.alloc(t.size(k));
         if (k > 0 && k + 1 < d) W[k] = DevBuf(h, t.size(k) * 8);
-        if (k > 0 && t.r[k] <= 256) {   // (r > 256: Z came from factor_big)
-            tb.L[ninv] = Lf[k].d();
-            tb.Dinv[ninv] = dinv[k];
-            tb.X[ninv] = Z[k].d();
-            tb.n[ninv] = int(t.r[k]);
-            ++ninv;
-        }
-    }
-    for (int b0 = 0; b0 < ninv; b0 += kTrinvBatchMax) {
-        TrinvBatch part{};
-        const int c = std::min(kTrinvBatchMax, ninv - b0);
-        for (int i = 0; i < c; ++i) {
-            part.L[i] = tb.L[b0 + i];
-            part.Dinv[i] = tb.Dinv[b0 + i];
-            part.X[i] = tb.X[b0 + i];
-            part.n[i] = tb.n[b0 + i];
-        }
-        trinv_batched(h, part, c);
     }
     // L_k and Z_k of the register-resident kernels (r <= 256) hold exact zeros above the diagonal: their
     // zero K-blocks are skipped (5/8 of the work at r = 256)
@@ -710,12 +445,9 @@ void chain_pass(TT& t, bool certify, ChainPass& out, int* host_status) {
 // True when every factorisation of the pass succeeded (valid after the stream has been synchronised).
 bool chain_status_ok(const ChainPass& p) {
     static const bool dbg = std::getenv("XRS_DEBUG_ROUND") != nullptr;
-    const int per = p.certify ? 3 : 1;
     for (int i = 0; i < p.count; ++i)
         if (p.status[i] != 0) {
-            if (dbg)
-                std::fprintf(stderr, "chain_pass: factorisation %d of %d (%d per edge r <= 256, then 2 per r > 256 "
-                             "job) failed at column %d\n", i, p.count, per, p.status[i]);
+            if (dbg) std::fprintf(stderr, "chain_pass: status word %d of %d is %d (a factorisation failed)\n", i, p.count, p.status[i]);
             return false;
         }
     return true;
@@ -751,7 +483,7 @@ double chain_check(TT& t, const std::vector<double*>& C) {
     constexpr int kSlices = 16;
     hipLaunchKernelGGL(k_dev_identity_many, dim3(nchk, kSlices), dim3(256), 0, h->stream, da);
     check_launch("k_dev_identity_many");
-    double* hd = static_cast<double*>(h->host_scratch) + 64;
+    double* hd = scratch::host<double>(h, scratch::kHostChainDev, size_t(nchk) * kSlices);
     XRS_HIP(hipMemcpyAsync(hd, dev.d(), size_t(nchk) * kSlices * 8, hipMemcpyDeviceToHost, h->stream));
     XRS_MARK("enq");
     host_wait(h);
@@ -775,12 +507,10 @@ bool round_chain(TT& t, const size_t* max_ranks, double eps) {
         if (t.r[k] > max_ranks[k - 1] || t.r[k] > kHugeMax) return false;
     const double cX = 0.5 * std::sqrt(kGramShift);
     if (!(eps < 0.25 * cX * cX)) return false;
-    // factorisation statuses (<= 3*64 ints) in a region of the pinned scratch no other routine uses
-    int* hs = static_cast<int*>(t.h->host_scratch) + 12288;
     HostMarks marks;
     g_marks = marks.on ? &marks : nullptr;
     ChainPass p1;
-    chain_pass(t, true, p1, hs);
+    chain_pass(t, true, p1);
     double dev = chain_check(t, p1.C);
     if (!chain_status_ok(p1)) {
         for (size_t k = 0; k < d; ++k) t.release(p1.C[k]);
@@ -792,7 +522,7 @@ bool round_chain(TT& t, const size_t* max_ranks, double eps) {
         TT t2 = t;
         t2.core = C.data();
         ChainPass p2;
-        chain_pass(t2, false, p2, hs);
+        chain_pass(t2, false, p2);
         const double dev2 = chain_check(t2, p2.C);
         const bool ok2 = chain_status_ok(p2);
         if (dbg) std::fprintf(stderr, "round_chain: pass 2 orthogonality %.3e (factors %s)\n", dev2, ok2 ? "ok" : "failed");
@@ -819,9 +549,8 @@ bool round_chain(TT& t, const size_t* max_ranks, double eps) {
 // right-orthonormal -- the truncating round's output when its Gram-based cores missed the tolerance:
 // same tensor and ranks, orthonormality restored to ~u. False (cores untouched) if the pass failed.
 bool reorthonormalize(TT& t) {
-    int* hs = static_cast<int*>(t.h->host_scratch) + 12288;
     ChainPass p;
-    chain_pass(t, false, p, hs);
+    chain_pass(t, false, p);
     const double dev = chain_check(t, p.C);
     const bool ok = chain_status_ok(p) && dev <= kOrthTol;
     for (size_t k = 0; k < t.d; ++k) {
@@ -856,8 +585,8 @@ void rl_sweep(TT& t, const size_t* max_ranks, double eps, double cX, size_t from
     }
 }
 
-// pinned / device scratch of the range probe (slots no other routine uses)
-constexpr size_t kProbeMax = 960, kProbeHost = 7200, kProbeDev = 4096;
+// cores the range probe's pinned and device scratch regions hold (960)
+constexpr size_t kProbeMax = std::min(scratch::kHostRangeProbe.len, scratch::kDevRangeProbe.len) / 8;
 
 void probe_core_ranges(TT& t) {
     t.range_probed = false;
@@ -866,9 +595,9 @@ void probe_core_ranges(TT& t) {
     std::vector<const double*> x(t.core, t.core + t.d);
     std::vector<size_t> n(t.d);
     for (size_t k = 0; k < t.d; ++k) n[k] = t.size(k);
-    double* dev = static_cast<double*>(h->dev_scratch) + kProbeDev;
+    double* dev = scratch::dev<double>(h, scratch::kDevRangeProbe, t.d);
     norms_enqueue(h, x.data(), n.data(), int(t.d), dev);
-    XRS_HIP(hipMemcpyAsync(static_cast<double*>(h->host_scratch) + kProbeHost, dev, t.d * 8, hipMemcpyDeviceToHost, h->stream));
+    XRS_HIP(hipMemcpyAsync(scratch::host<double>(h, scratch::kHostRangeProbe, t.d), dev, t.d * 8, hipMemcpyDeviceToHost, h->stream));
     t.range_probed = true;
 }
 
@@ -878,7 +607,7 @@ void probe_core_ranges(TT& t) {
 // to more than 200 in magnitude (2^+-200 ~ 1e+-60): the scale a sweep or a Gram chain gathers in one factor,
 // which the Grams and the Jacobi dots then square
 static bool core_exponents(const TT& t, std::vector<int>& ex) {
-    const double* am = static_cast<const double*>(t.h->host_scratch) + kProbeHost;
+    const double* am = scratch::host<double>(t.h, scratch::kHostRangeProbe, t.d);
     ex.assign(t.d, 0);
     long prefix = 0, lo = 0, hi = 0;   // (largest |sum over a run| = max prefix sum - min prefix sum)
     for (size_t k = 0; k < t.d; ++k) {
@@ -994,7 +723,7 @@ double dot_two_ended(xrs_handle_t h, size_t d, const size_t* n, const size_t* rx
         else gemm(h, g);
     };
     if (!unit_l || !unit_r) {
-        double* ones = static_cast<double*>(h->host_scratch) + 4096;   // (a slot no other routine uses)
+        double* ones = scratch::host<double>(h, scratch::kHostDotOnes, 2);
         ones[0] = ones[1] = 1.0;
         XRS_HIP(hipMemcpyAsync(P0.d(), &ones[0], 8, hipMemcpyHostToDevice, h->stream));
         XRS_HIP(hipMemcpyAsync(P0.d() + emax, &ones[1], 8, hipMemcpyHostToDevice, h->stream));
@@ -1082,7 +811,7 @@ double dot(xrs_handle_t h, size_t d, const size_t* n, const size_t* rx, const do
         if (shard) shard->reduce(En, a2 * b2);   // sum over all ranks' mode slices
         std::swap(E, En);
     }
-    double* hs = static_cast<double*>(h->host_scratch);
+    double* hs = scratch::host<double>(h, scratch::kHostResult);
     XRS_HIP(hipMemcpyAsync(hs, E, 8, hipMemcpyDeviceToHost, h->stream));
     host_wait(h);
     return hs[0];

@@ -3,6 +3,8 @@
 #pragma once
 #include <vector>
 
+#include "chol_batch.hpp"
+#include "scratch_map.hpp"
 #include "smallla.hpp"
 
 namespace xrs {
@@ -117,19 +119,9 @@ struct GemmJob {
 };
 void gemm_grouped(xrs_handle_t h, const std::vector<GemmJob>& jobs);
 
-// Cholesky (+ explicit inverse) of 256 < n <= 512 matrices from the n <= 256 kernels (2 x 2 blocks)
-constexpr int kBigMax = 64;
 // largest rank of the certified chain / truncating rounds (blocked Cholesky above 512, the 1024-column
 // register tiling of the block Jacobi SVD)
 constexpr size_t kHugeMax = 1024;
-struct BigJob {
-    const double* src;
-    double shift_rel;
-    int n;
-    double* L;   // factor jobs: full L and Z = L^{-1} (n x n); certificates: both null
-    double* Z;
-};
-void factor_big(xrs_handle_t h, const std::vector<BigJob>& jobs, int* status, std::vector<DevBuf>& keep);
 
 // the reference's two-sweep algorithm pieces (sequential, host-synchronising)
 void transfer_right(TT& t, size_t k, bool rank_reduce);   // transfer_core(k -> k+1): QC (or QR) + R * next

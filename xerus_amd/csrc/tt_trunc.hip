@@ -64,79 +64,6 @@ struct Sweep {
     }
 };
 
-// one or more Cholesky factorisations of an n x n symmetric matrix in a single launch (n <= 512; larger
-// ones blocked, one job at a time):
-// the factor L (lower, out of place) and its inverse Z = L^{-1}, plus status-only certificates
-// chol(A - tau tr(A) I). Statuses go to status[0..count).
-struct CholJob {
-    const double* A;
-    int n;
-    double* L;   // null: certificate only
-    double* Z;
-    double shift = 0.0;   // relative diagonal shift (factor jobs; certificates always -kGramShift)
-};
-
-void chol_jobs(Sweep& sw, const std::vector<CholJob>& jobs, int* status) {
-    xrs_handle_t h = sw.t.h;
-    std::vector<BigJob> big;
-    std::vector<int> big_slot;
-    PotrfBatch pb{};
-    TrinvBatch tb{};
-    int ns = 0, ninv = 0;
-    std::vector<int> huge;
-    for (size_t i = 0; i < jobs.size(); ++i) {
-        const CholJob& j = jobs[i];
-        if (j.n > 512) {   // blocked, one job at a time (ranks above the batched kernels)
-            huge.push_back(int(i));
-            continue;
-        }
-        if (j.n > 256) {
-            big.push_back({j.A, j.L ? j.shift : -kGramShift, j.n, j.L, j.Z});
-            big_slot.push_back(int(i));
-            continue;
-        }
-        XRS_REQUIRE(ns < kPotrfBatchMax, "chol_jobs: batch too large");
-        double* dinv = j.L ? sw.buf(dinv_elems(j.n)) : sw.buf(dinv_elems(j.n));
-        pb.src[ns] = j.A;
-        pb.G[ns] = j.L;
-        pb.Dinv[ns] = dinv;
-        pb.shift[ns] = j.L ? j.shift : -kGramShift;
-        pb.n[ns] = j.n;
-        ++ns;
-        if (j.L && j.Z) {
-            tb.L[ninv] = j.L;
-            tb.Dinv[ninv] = dinv;
-            tb.X[ninv] = j.Z;
-            tb.n[ninv] = j.n;
-            ++ninv;
-        }
-    }
-    // statuses: the small jobs first in job order is not needed -- keep one slot per small job, then two
-    // per big job (factor_big's two diagonal blocks); the caller only tests all-zero
-    if (ns) {
-        pb.status = status;
-        potrf_batched(h, pb, ns);
-    }
-    if (ninv) trinv_batched(h, tb, ninv);
-    if (!big.empty()) {
-        std::vector<DevBuf> keep;
-        factor_big(h, big, status + ns, keep);
-        for (auto& k : keep) sw.keep.push_back(std::move(k));
-    }
-    int slot = ns + 2 * int(big.size());
-    for (int i : huge) {
-        const CholJob& j = jobs[size_t(i)];
-        chol_full(h, j.A, size_t(j.n), j.L ? j.shift : -kGramShift, j.L, j.Z, status + slot);
-        slot += chol_full_blocks(size_t(j.n));
-    }
-}
-
-int chol_status_count(const std::vector<CholJob>& jobs) {
-    int c = 0;
-    for (const CholJob& j : jobs) c += j.n > 512 ? chol_full_blocks(size_t(j.n)) : (j.n > 256 ? 2 : 1);
-    return c;
-}
-
 // max |X X^T - I| (rows, `rows` = true) or max |X^T X - I| of a list of matrices -> dev[0..count*16);
 // the Grams sit in one buffer, completed across ranks by ONE all-reduce when sharded
 void orth_devs(Sweep& sw, const std::vector<const double*>& X, const std::vector<size_t>& m, const std::vector<size_t>& n,
@@ -203,13 +130,10 @@ void left_pass(Sweep& sw, TT& t0, double* const* src, bool certify, std::vector<
         Lf[k] = sw.buf(size_t(a) * a);
         Zf[k] = sw.buf(size_t(a) * a);
         jobs.push_back({G[k], a, Lf[k], Zf[k], shift});
-        if (certify) jobs.push_back({G[k], a, nullptr, nullptr});
+        if (certify) jobs.push_back(CholJob::certificate(G[k], a, kGramShift));
     }
-    for (size_t b0 = 0; b0 < jobs.size(); b0 += 40) {   // (potrf_batched / trinv tables hold 48 / 64)
-        const std::vector<CholJob> part(jobs.begin() + long(b0), jobs.begin() + long(std::min(jobs.size(), b0 + 40)));
-        chol_jobs(sw, part, status + nst);
-        nst += chol_status_count(part);
-    }
+    chol_enqueue(h, jobs, status + nst, sw.keep);
+    nst += chol_status_count(jobs);
     A.assign(d, nullptr);
     std::vector<double*> W(d, nullptr);
     std::vector<GemmJob> lefts, rights;
@@ -250,9 +174,7 @@ ShardLayout shard_layout(TT& t) {
     xrs_handle_t h = t.h;
     const size_t w = t.world > 0 ? size_t(t.world) : 1, me = t.world > 0 ? size_t(t.rank) : 0;
     XRS_REQUIRE(w * d <= 2040 && me < w, "shard_layout: world / rank out of range");
-    // (pinned scratch: doubles 4100 .. 6140, a region no other routine uses -- 2048.. the check points'
-    // deviations, 4096 dot_two_ended's unit environments, 6144.. the status words)
-    double* hn = static_cast<double*>(h->host_scratch) + 4100;
+    double* hn = scratch::host<double>(h, scratch::kHostShardLayout, w * d);
     for (size_t i = 0; i < w * d; ++i) hn[i] = 0.0;
     for (size_t k = 0; k < d; ++k) hn[me * d + k] = double(t.n[k]);
     DevBuf tab(h, w * d * 8);
@@ -353,6 +275,8 @@ bool round_truncate(TT& t, const size_t* max_ranks, double eps) {
     Sweep sw(t);
     // statuses: factorisations from 0 up, Jacobi convergence at kJacobiSlot + edge
     constexpr int kStatusWords = 1024, kJacobiSlot = 768;
+    // (a left pass or a sweep: at most d - 1 <= 63 edges x 2 jobs x the 4 status words of a 1024 x 1024 job)
+    static_assert(63 * 2 * 4 <= kJacobiSlot && kHugeMax <= 1024);
     DevBuf st(h, kStatusWords * 4), devb(h, 64 * 16 * 8);
     int* status = st.as<int>();
     int nst = 0;
@@ -360,8 +284,8 @@ bool round_truncate(TT& t, const size_t* max_ranks, double eps) {
 
     // 1b. left chain pass (certified), and a second one on its output when a single CholeskyQR pass over
     //     the train left the cores short of orthonormal (kappa^2 u > tol: CholeskyQR2 on the whole train)
-    int* hs = static_cast<int*>(h->host_scratch) + 13312;
-    double* hd = static_cast<double*>(h->host_scratch) + 2048;
+    int* hs = scratch::host<int>(h, scratch::kHostTruncStatus, kStatusWords);
+    double* hd = scratch::host<double>(h, scratch::kHostTruncDev, (d - 1) * 16);
     std::vector<double*> A;
     left_pass(sw, t, t.core, true, A, status, nst);
     double worst = 0.0;
@@ -417,17 +341,21 @@ bool round_truncate(TT& t, const size_t* max_ranks, double eps) {
     // handle owns its streams and is not inside a fork
     const bool cert_side = !h->borrowed_streams && h->stream == h->own_stream && h->side_stream[0] && h->prof_mask == 0;
     bool side_used = false;
-    struct : PotrfBatch { int count = 0; } pending_cert{};
+    auto enqueue_chol = [&](const std::vector<CholJob>& jobs) {
+        const int c = chol_status_count(jobs);
+        XRS_REQUIRE(nst + c <= kJacobiSlot, "round_truncate: too many factorisation statuses");
+        chol_enqueue(h, jobs, status + nst, sw.keep);
+        nst += c;
+    };
+    std::vector<CholJob> pending_cert;
     auto flush_certs = [&]() {
-        if (pending_cert.count == 0) return;
-        pending_cert.status = status + nst;
+        if (pending_cert.empty()) return;
         XRS_HIP(hipEventRecord(h->ev_fork, h->stream));
         XRS_HIP(hipStreamWaitEvent(h->side_stream[0], h->ev_fork, 0));
         side_used = true;
         StreamSwap on_side(h, h->side_stream[0]);   // (restores h->stream on scope exit, also on a throw)
-        potrf_batched(h, pending_cert, pending_cert.count);
-        nst += pending_cert.count;
-        pending_cert.count = 0;
+        enqueue_chol(pending_cert);
+        pending_cert.clear();
     };
     for (size_t k = d - 1; k >= 1; --k) {
         const size_t r = rr[k], N = t.n[k] * rr[k + 1], Ng = ng[k] * rr[k + 1];   // local / global columns
@@ -464,26 +392,17 @@ bool round_truncate(TT& t, const size_t* max_ranks, double eps) {
         static const bool force_jacobi = std::getenv("XRS_TRUNC_JACOBI") != nullptr;
         const bool use_eig = !force_jacobi && sym_eig_top_fits(int(g), int(kk));
         double* L = use_eig ? nullptr : sw.buf(g * g);
-        double* Z = (!use_eig && g > 256) ? sw.buf(g * g) : nullptr;   // (factor_big always builds L^{-1})
         if (use_eig && cert_side) {
             // the eigensolver does not need the factor: the status-only certificates run on a side stream
             // beside it (their statuses are read after the one join before the final check), batched: edges
             // d-1 .. 2 in one launch forked behind edge 2's P, edge 1 on its own (a fork per edge left a
             // ~7 us gap before every tridiagonalisation: the event record on the main stream)
-            const int slot = pending_cert.count;
-            XRS_REQUIRE(slot < kPotrfBatchMax, "round_truncate: too many certificates");
-            pending_cert.src[slot] = P;
-            pending_cert.G[slot] = nullptr;
-            pending_cert.Dinv[slot] = sw.buf(dinv_elems(int(g)));
-            pending_cert.shift[slot] = -kGramShift;
-            pending_cert.n[slot] = int(g);
-            pending_cert.count = slot + 1;
-            if (k <= 2 || slot + 1 == kPotrfBatchMax) flush_certs();
+            pending_cert.push_back(CholJob::certificate(P, int(g), kGramShift));
+            if (k <= 2 || int(pending_cert.size()) == kCholLaunchJobs) flush_certs();   // (a full launch)
         } else {
-            std::vector<CholJob> cj{{P, int(g), nullptr, nullptr}};
-            if (!use_eig) cj.insert(cj.begin(), CholJob{P, int(g), L, Z});
-            chol_jobs(sw, cj, status + nst);
-            nst += chol_status_count(cj);
+            std::vector<CholJob> cj{CholJob::certificate(P, int(g), kGramShift)};
+            if (!use_eig) cj.insert(cj.begin(), CholJob{P, int(g), L, nullptr});
+            enqueue_chol(cj);
         }
         double* S = sw.buf(g);
         double* Vt = (wide || tall_gather) ? sw.buf(g * g) : sw.core(g * g);
@@ -767,7 +686,7 @@ bool round_general(TT& t, const size_t* max_ranks, double eps) {
 
     std::vector<double*> A(t.core, t.core + d);   // current cores (originals untouched)
     std::vector<size_t> rr(t.r, t.r + d + 1);
-    int* hs = static_cast<int*>(h->host_scratch) + 12288;
+    int* hs = scratch::host<int>(h, scratch::kHostGeneralStatus, kSlots);
 
     // 1a. left to right as shifted CholeskyQR3 over the whole train: three chain passes (Gram chain
     //     G_{k+1} = M_k^T (G_k (x) I) M_k, ONE batched Cholesky launch of G_k + s tr(G_k) I (first pass) /
@@ -817,7 +736,7 @@ bool round_general(TT& t, const size_t* max_ranks, double eps) {
             }
             orth_devs(sw, X, m, n, false, devb.d());
         }
-        double* hd = static_cast<double*>(h->host_scratch) + 2048;
+        double* hd = scratch::host<double>(h, scratch::kHostTruncDev, (d - 1) * 16);
         const int nchk = int(d - 1) * 16;
         XRS_HIP(hipMemcpyAsync(hs, st, size_t(cst) * 4, hipMemcpyDeviceToHost, h->stream));
         XRS_HIP(hipMemcpyAsync(hd, devb.d(), size_t(nchk) * 8, hipMemcpyDeviceToHost, h->stream));
@@ -1010,7 +929,7 @@ bool round_general(TT& t, const size_t* max_ranks, double eps) {
         }
         orth_devs(sw, X, m, n, true, devb.d());
     }
-    double* hd = static_cast<double*>(h->host_scratch) + 2048;
+    double* hd = scratch::host<double>(h, scratch::kHostTruncDev, (d - 1) * 16);
     const int nchk = int(d - 1) * 16;
     XRS_HIP(hipMemcpyAsync(hd, devb.d(), size_t(nchk) * 8, hipMemcpyDeviceToHost, h->stream));
     host_wait(h);

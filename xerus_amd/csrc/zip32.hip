@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "runtime.hpp"
+#include "scratch_map.hpp"
 #include "sgemm.hpp"
 #include "tt_internal.hpp"
 
@@ -834,9 +835,9 @@ double run(xrs_handle_t h, size_t d, const size_t* n, const size_t* rx, const do
     else hipLaunchKernelGGL((k_zfinish<float, float>), fg, dim3(256), 0, h->stream, static_cast<const float*>(cur[0]), static_cast<const float*>(cur[1]), nm, part, slots, cmax_out);
     check_launch("k_zfinish");
     // ---- read back: partials, then the words (exponents, core maxima)
-    char* hs = static_cast<char*>(h->host_scratch);
+    char* hs = static_cast<char*>(h->host_scratch);   // (the whole area: no other user is live beside a zipper)
     const size_t back = o_words - o_part + 4 * nwords;
-    XRS_REQUIRE(back <= (size_t(1) << 16), "fused fp32 zipper: read-back exceeds the host scratch");
+    XRS_REQUIRE(back <= scratch::kBytes, "fused fp32 zipper: read-back exceeds the host scratch");
     XRS_HIP(hipMemcpyAsync(hs, part, back, hipMemcpyDeviceToHost, h->stream));
     host_wait(h);
     const int* hw = reinterpret_cast<const int*>(hs + (o_words - o_part));
