@@ -15,6 +15,7 @@
 #include "xerus/algorithms/cg.h"
 #include "xerus/measurments.h"
 #include "xerus/algorithms/adf.h"
+#include "xerus/algorithms/uqAdf.h"
 
 namespace xerus {
 namespace gpu {

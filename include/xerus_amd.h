@@ -341,6 +341,21 @@ int xrs_tt_dot_sharded(xrs_handle_t handle, double* result, size_t d, const size
                        const double* const* X, const size_t* ry, const double* const* Y, xrs_allreduce_fn allreduce,
                        void* ctx);
 
+/* ---------------------------------------------------------------- UQ-ADF per-sample stacks (uqAdf.cpp:40-282) */
+/** P (N x n) from xi (N): P[j, i] = He_i(xi[j]), the probabilists' Hermite polynomials He_0 = 1, He_1 = v,
+ *  He_{i+1} = v He_i - i He_{i-1} (replaces randVar_to_position, uqAdf.cpp:40-52, for all samples at once). */
+int xrs_uq_basis(xrs_handle_t handle, double* P, const double* xi, size_t N, size_t n);
+/** Lout[j] (b x b) = M_j^T Lprev[j] M_j for every sample j < N, M_j = sum_t P[j, t] X[:, t, :] (a x b) for the
+ *  component X (a x n x b) and the basis rows P (N x n); Lprev (N x a x a) symmetric, NULL = the identity
+ *  (replaces the leftIsStack loop of calc_left_stack, uqAdf.cpp:126-135). M_j and Lprev[j] M_j stay on chip;
+ *  Lout[j] is exactly symmetric. 1 <= a, b <= 256, else XRS_EINVAL. Lout must not alias Lprev. */
+int xrs_uq_stack_congruence(xrs_handle_t handle, double* Lout, const double* Lprev, const double* X, const double* P,
+                            size_t N, size_t a, size_t n, size_t b);
+/** *result = sum_j V[j]^T L[j] V[j], V (N x a), L (N x a x a) symmetric, NULL = the identity (replaces the loop of
+ *  calculate_norm_A_projGrad, uqAdf.cpp:241-261). Fixed-order two-level reduction (bit-reproducible).
+ *  1 <= a <= 256, else XRS_EINVAL. Synchronises. */
+int xrs_uq_quadform(xrs_handle_t handle, double* result, const double* L, const double* V, size_t N, size_t a);
+
 /* ---------------------------------------------------------------- profiling */
 /** Kernel-duration instrumentation: while enabled, every launch of a kernel whose family id is in
  *  `family_mask` is bracketed by HIP events on the handle's stream. */

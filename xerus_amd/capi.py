@@ -95,6 +95,9 @@ SIGNATURES = {
     "xrs_tt_gather_sharded": (C.c_int, [_DP, _SZ, C.POINTER(_SZ), C.c_int, C.c_int, C.POINTER(_SZ), C.POINTER(_DP),
                                         C.POINTER(_DP), _DP, _DP]),
     "xrs_tt_shard": (C.c_int, [_DP, _SZ, C.POINTER(_SZ), C.c_int, C.c_int, C.POINTER(_SZ), C.POINTER(_DP), C.POINTER(_DP)]),
+    "xrs_uq_basis": (C.c_int, [_DP, _DP, _DP, _SZ, _SZ]),
+    "xrs_uq_stack_congruence": (C.c_int, [_DP, _DP, _DP, _DP, _DP, _SZ, _SZ, _SZ, _SZ]),
+    "xrs_uq_quadform": (C.c_int, [_DP, C.POINTER(C.c_double), _DP, _DP, _SZ, _SZ]),
     "xrs_prof_begin": (C.c_int, [_DP, C.c_uint32]),
     "xrs_prof_end": (C.c_int, [_DP, C.POINTER(_SZ), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                C.POINTER(C.c_double)]),
@@ -363,6 +366,30 @@ class Handle:
             res.append(arr.numpy())
             self.free(out[k])
         return res
+
+    def uq_basis(self, xi: "DeviceArray", n: int) -> "DeviceArray":
+        """xrs_uq_basis: the N x n Hermite basis matrix of the N random variables xi."""
+        N = xi.size
+        P = self.empty((N, n))
+        _check("xrs_uq_basis", self.lib.xrs_uq_basis(self.h, _DP(P.ptr), _DP(xi.ptr), N, n))
+        return P
+
+    def uq_stack_congruence(self, Lprev: "DeviceArray | None", X: "DeviceArray", P: "DeviceArray") -> "DeviceArray":
+        """xrs_uq_stack_congruence: the N x b x b stack M_j^T Lprev_j M_j (Lprev None: the identity)."""
+        a, n, b = X.shape
+        N = P.shape[0]
+        out = self.empty((N, b, b))
+        _check("xrs_uq_stack_congruence", self.lib.xrs_uq_stack_congruence(
+            self.h, _DP(out.ptr), _DP(Lprev.ptr) if Lprev is not None else None, _DP(X.ptr), _DP(P.ptr), N, a, n, b))
+        return out
+
+    def uq_quadform(self, L: "DeviceArray | None", V: "DeviceArray") -> float:
+        """xrs_uq_quadform: sum_j V_j^T L_j V_j (L None: the identity)."""
+        N, a = V.shape
+        r = C.c_double()
+        _check("xrs_uq_quadform", self.lib.xrs_uq_quadform(self.h, C.byref(r), _DP(L.ptr) if L is not None else None,
+                                                          _DP(V.ptr), N, a))
+        return r.value
 
     def last_round_path(self) -> str | None:
         """"chain" / "truncate" / "general" / "reference": the algorithm of this handle's last TT round."""

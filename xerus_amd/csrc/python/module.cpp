@@ -561,6 +561,35 @@ PYBIND11_MODULE(xerus, m) {
             return _v(_x, _m, _r);
         });
     m.attr("ADF") = py::cast(ADFVariant(ADF));
+
+    // ------------------------------------------------------------------ UQ-ADF (algorithms/uqAdf.h)
+    py::class_<UQMeasurementSet>(m, "UQMeasurementSet")
+        .def(py::init<>())
+        .def(py::init<const UQMeasurementSet&>())
+        .def_readwrite("randomVectors", &UQMeasurementSet::randomVectors)
+        .def_readwrite("solutions", &UQMeasurementSet::solutions)
+        .def_readwrite("initialRandomVectors", &UQMeasurementSet::initialRandomVectors)
+        .def_readwrite("initialSolutions", &UQMeasurementSet::initialSolutions)
+        .def("add", &UQMeasurementSet::add)
+        .def("add_initial", &UQMeasurementSet::add_initial);
+    m.def("randVar_to_position", &randVar_to_position, py::arg("v"), py::arg("polyDegree"));
+    m.def("uq_adf", [](TTTensor& _x, const std::vector<std::vector<double>>& _rv, const std::vector<Tensor>& _sol) { uq_adf(_x, _rv, _sol); },
+          py::arg("x"), py::arg("randomVariables"), py::arg("solutions"));
+    // the extended overload: returns the relative residual of every iteration
+    m.def("uq_adf", [](TTTensor& _x, const std::vector<std::vector<double>>& _rv, const std::vector<Tensor>& _sol, size_t _maxIterations) {
+        std::vector<double> history;
+        uq_adf(_x, _rv, _sol, _maxIterations, &history);
+        return history;
+    }, py::arg("x"), py::arg("randomVariables"), py::arg("solutions"), py::arg("maxIterations"));
+    m.def("uq_adf", [](const UQMeasurementSet& _m, const TTTensor& _guess) { return uq_adf(_m, _guess); }, py::arg("measurments"),
+          py::arg("guess"));
+    m.def("uq_adf", [](const UQMeasurementSet& _m, const TTTensor& _guess, size_t _maxIterations) {
+        std::vector<double> history;
+        TTTensor x = uq_adf(_m, _guess, _maxIterations, &history);
+        return std::make_pair(std::move(x), std::move(history));
+    }, py::arg("measurments"), py::arg("guess"), py::arg("maxIterations"));
+    m.def("uq_mc", &uq_mc, py::arg("x"), py::arg("N"), py::arg("numSpecial"));
+    m.def("uq_avg", &uq_avg, py::arg("x"), py::arg("N"), py::arg("numSpecial"));
     m.def("solve", [](const Tensor& _A, const Tensor& _B, size_t _extra) {
         Tensor X;
         solve(X, _A, _B, _extra);
