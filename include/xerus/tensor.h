@@ -185,6 +185,10 @@ void solve(Tensor& _X, const Tensor& _A, const Tensor& _B, const size_t _extraDe
 void solve_least_squares(Tensor& _X, const Tensor& _A, const Tensor& _B, const size_t _extraDegree = 0);
 void calculate_svd(Tensor& _U, Tensor& _S, Tensor& _Vt, Tensor _input, const size_t _splitPos, const size_t _maxRank,
                    const value_t _eps);
+/// calculate_svd of every input (same contract, outputs in input order): inputs whose unfoldings at _splitPos share
+/// their (rows, columns) are factored together, one batched device call (xrs_svd_batched) per shape
+void calculate_svd(std::vector<Tensor>& _U, std::vector<Tensor>& _S, std::vector<Tensor>& _Vt, const std::vector<Tensor>& _inputs,
+                   const size_t _splitPos, const size_t _maxRank, const value_t _eps);
 void calculate_qr(Tensor& _Q, Tensor& _R, Tensor _input, const size_t _splitPos);
 void calculate_rq(Tensor& _R, Tensor& _Q, Tensor _input, const size_t _splitPos);
 void calculate_qc(Tensor& _Q, Tensor& _C, Tensor _input, const size_t _splitPos);

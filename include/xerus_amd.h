@@ -135,6 +135,19 @@ int xrs_rq(xrs_handle_t handle, double* R, double* Q, const double* A, size_t m,
 /** Thin SVD A = U*diag(S)*Vt, U: m x k, S: k, Vt: k x n, k = min(m,n), S descending
  *  (replaces blasWrapper::svd / dgesdd 'S', blasLapackWrapper.cpp:201-232). */
 int xrs_svd(xrs_handle_t handle, double* U, double* S, double* Vt, const double* A, size_t m, size_t n);
+/** Thin SVDs of `batch` m x n matrices stored back to back (A: batch*m*n; U: batch*m*k; S: batch*k;
+ *  Vt: batch*k*n; k = min(m,n); each as xrs_svd). status (host, batch ints, may be NULL): sweeps of the
+ *  batched kernel, or -1 where the member was recomputed by the single-matrix route. Synchronises once.
+ *  One launch (a workgroup per matrix, one-sided Jacobi in LDS) while p = min(m,n), q = max(m,n) satisfy
+ *  p + q <= 512 and 8 (p ld + p + 8) + 4 (p + 2) <= 160 KiB, ld = p + q rounded up to 16 mod 32 (64 x 64 and
+ *  32 x 448 fit, 128 x 128 does not); members that are not of full numerical rank, and every member of a
+ *  shape outside that envelope, go through xrs_svd's route one by one (inside the envelope their U and Vt
+ *  are then re-orthonormalised, so zero and rounding-size singular values get orthonormal vectors too, where
+ *  xrs_svd alone may return zero or non-orthogonal ones). batch = 0 is a no-op. */
+int xrs_svd_batched(xrs_handle_t handle, double* U, double* S, double* Vt, int* status,
+                    const double* A, size_t batch, size_t m, size_t n);
+/** 1 if m x n matrices are inside the batched kernel's envelope (see above), else 0. Needs no handle. */
+int xrs_svd_batched_fits(size_t m, size_t n);
 /** Solve A X = B, A m x n, B m x p, X n x p (replaces blasWrapper::solve, blasLapackWrapper.cpp:540-640):
  *  the reference's dispatch (m != n: least squares; not symmetric: general; symmetric with a positive
  *  diagonal: Cholesky, falling back to the general path). Cholesky is blocked (any n); the general and

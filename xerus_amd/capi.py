@@ -51,6 +51,8 @@ SIGNATURES = {
     "xrs_qr": (C.c_int, [_DP, _DP, _DP, _DP, _SZ, _SZ]),
     "xrs_rq": (C.c_int, [_DP, _DP, _DP, _DP, _SZ, _SZ]),
     "xrs_svd": (C.c_int, [_DP, _DP, _DP, _DP, _DP, _SZ, _SZ]),
+    "xrs_svd_batched": (C.c_int, [_DP, _DP, _DP, _DP, C.POINTER(C.c_int), _DP, _SZ, _SZ, _SZ]),
+    "xrs_svd_batched_fits": (C.c_int, [_SZ, _SZ]),
     "xrs_solve": (C.c_int, [_DP, _DP, _DP, _SZ, _SZ, _DP, _SZ]),
     "xrs_solve_least_squares": (C.c_int, [_DP, _DP, _DP, _SZ, _SZ, _DP, _SZ]),
     "xrs_svd_rows_vt": (C.c_int, [_DP, _DP, _DP, C.POINTER(C.c_int), _DP, _SZ, _SZ, C.c_int]),
@@ -138,6 +140,11 @@ def load(path: str | None = None) -> C.CDLL:
 def _check(fn: str, status: int):
     if status != 0:
         raise XrsError(fn, status, load().xrs_last_error().decode())
+
+
+def svd_batched_fits(m: int, n: int) -> bool:
+    """Whether Handle.svd_batched factors m x n members in its batched kernel (else one by one); needs no GPU."""
+    return bool(load().xrs_svd_batched_fits(int(m), int(n)))
 
 
 def _arr(vals: Sequence[int]):
@@ -318,6 +325,19 @@ class Handle:
         U, S, Vt = self.empty((m, k)), self.empty((k,)), self.empty((k, n))
         _check("xrs_svd", self.lib.xrs_svd(self.h, _DP(U.ptr), _DP(S.ptr), _DP(Vt.ptr), _DP(A.ptr), m, n))
         return U, S, Vt
+
+    def svd_batched(self, A: "DeviceArray", want_status: bool = True):
+        """(U, S, Vt, status) of the thin SVDs of A[b] (A: batch x m x n) in one call (xrs_svd_batched).
+        status[b]: sweeps of the batched kernel, or -1 where member b went through the single-matrix route
+        (None with want_status=False: the C call then gets status = NULL)."""
+        batch, m, n = A.shape
+        k = min(m, n)
+        U, S, Vt = self.empty((batch, m, k)), self.empty((batch, k)), self.empty((batch, k, n))
+        st = np.zeros(batch, dtype=np.intc) if want_status else None
+        _check("xrs_svd_batched", self.lib.xrs_svd_batched(
+            self.h, _DP(U.ptr), _DP(S.ptr), _DP(Vt.ptr), st.ctypes.data_as(C.POINTER(C.c_int)) if want_status else None,
+            _DP(A.ptr), batch, m, n))
+        return U, S, Vt, st
 
     def solve(self, A: "DeviceArray", B: "DeviceArray", least_squares: bool = False):
         """X with A X = B (xrs_solve; least_squares: xrs_solve_least_squares). B: m x p (or length m)."""

@@ -10,6 +10,7 @@
 #include <numeric>
 
 #include "../smallla.hpp"
+#include "../svd_batched.hpp"
 #include "xerus.h"
 
 namespace xerus {
@@ -655,21 +656,12 @@ void solve_least_squares(Tensor& _X, const Tensor& _A, const Tensor& _B, const s
     solve_impl(_X, _A, _B, _extraDegree, true);
 }
 
-void calculate_svd(Tensor& _U, Tensor& _S, Tensor& _Vt, Tensor _input, const size_t _splitPos, const size_t _maxRank,
-                   const value_t _eps) {
-    XERUS_REQUIRE(0 <= _eps && _eps < 1, "Epsilon must be fullfill 0 <= _eps < 1.");
-    size_t m, n;
-    factorization_sizes(_input, _splitPos, m, n);
+// The rank cut and the output tensors of calculate_svd from the device factors Ud (m x k), Vtd (k x n) and
+// the host copy s (k) of the singular values of _input's unfolding at _splitPos.
+static void svd_outputs(Tensor& _U, Tensor& _S, Tensor& _Vt, const Tensor& _input, const size_t _splitPos, const size_t _maxRank,
+                        const value_t _eps, const size_t m, const size_t n, const double* Ud, const double* Vtd, const double* s) {
     const size_t k = std::min(m, n);
     xrs_handle_t h = gpu::handle();
-    xrs::DevBuf U(h, m * k * 8), S(h, k * 8), Vt(h, k * n * 8);
-    const double* A = _input.device_data();
-    guard([&] { xrs::svd(h, A, m, n, U.d(), S.d(), Vt.d()); });
-    std::vector<double> s(k);
-    guard([&] {
-        XRS_HIP(hipMemcpyAsync(s.data(), S.d(), k * 8, hipMemcpyDeviceToHost, h->stream));
-        XRS_HIP(hipStreamSynchronize(h->stream));
-    });
     size_t rank = k;
     if (_maxRank != 0) rank = std::min(rank, _maxRank);
     for (size_t j = 1; j < rank; ++j) {
@@ -682,8 +674,8 @@ void calculate_svd(Tensor& _U, Tensor& _S, Tensor& _Vt, Tensor _input, const siz
     Tensor Vtt(dims_with(_input.dimensions, _splitPos, _input.degree(), rank, true), Tensor::Representation::Dense,
                Tensor::Initialisation::None);
     guard([&] {
-        XRS_HIP(hipMemcpy2DAsync(Ut.device_data_for_write(), rank * 8, U.d(), k * 8, rank * 8, m, hipMemcpyDeviceToDevice, h->stream));
-        XRS_HIP(hipMemcpyAsync(Vtt.device_data_for_write(), Vt.d(), rank * n * 8, hipMemcpyDeviceToDevice, h->stream));
+        XRS_HIP(hipMemcpy2DAsync(Ut.device_data_for_write(), rank * 8, Ud, k * 8, rank * 8, m, hipMemcpyDeviceToDevice, h->stream));
+        XRS_HIP(hipMemcpyAsync(Vtt.device_data_for_write(), Vtd, rank * n * 8, hipMemcpyDeviceToDevice, h->stream));
     });
     if (!(s[0] > 0.0)) {
         // the zero matrix: rank 1 with sigma 0; dgesdd's factors are still orthonormal (e_0 columns / rows)
@@ -705,6 +697,64 @@ void calculate_svd(Tensor& _U, Tensor& _S, Tensor& _Vt, Tensor _input, const siz
     _U = std::move(Ut);
     _S = std::move(St);
     _Vt = std::move(Vtt);
+}
+
+void calculate_svd(Tensor& _U, Tensor& _S, Tensor& _Vt, Tensor _input, const size_t _splitPos, const size_t _maxRank,
+                   const value_t _eps) {
+    XERUS_REQUIRE(0 <= _eps && _eps < 1, "Epsilon must be fullfill 0 <= _eps < 1.");
+    size_t m, n;
+    factorization_sizes(_input, _splitPos, m, n);
+    const size_t k = std::min(m, n);
+    xrs_handle_t h = gpu::handle();
+    xrs::DevBuf U(h, m * k * 8), S(h, k * 8), Vt(h, k * n * 8);
+    const double* A = _input.device_data();
+    guard([&] { xrs::svd(h, A, m, n, U.d(), S.d(), Vt.d()); });
+    std::vector<double> s(k);
+    guard([&] {
+        XRS_HIP(hipMemcpyAsync(s.data(), S.d(), k * 8, hipMemcpyDeviceToHost, h->stream));
+        XRS_HIP(hipStreamSynchronize(h->stream));
+    });
+    svd_outputs(_U, _S, _Vt, _input, _splitPos, _maxRank, _eps, m, n, U.d(), Vt.d(), s.data());
+}
+
+void calculate_svd(std::vector<Tensor>& _U, std::vector<Tensor>& _S, std::vector<Tensor>& _Vt, const std::vector<Tensor>& _inputs,
+                   const size_t _splitPos, const size_t _maxRank, const value_t _eps) {
+    XERUS_REQUIRE(0 <= _eps && _eps < 1, "Epsilon must be fullfill 0 <= _eps < 1.");
+    const size_t count = _inputs.size();
+    std::vector<std::pair<size_t, size_t>> shape(count);
+    for (size_t i = 0; i < count; ++i) factorization_sizes(_inputs[i], _splitPos, shape[i].first, shape[i].second);
+    std::vector<Tensor> Us(count), Ss(count), Vts(count);   // (the outputs may alias the inputs)
+    xrs_handle_t h = gpu::handle();
+    std::vector<bool> done(count, false);
+    for (size_t first = 0; first < count; ++first) {
+        if (done[first]) continue;
+        // the group of this shape, in input order; the members' (factor-free) data back to back
+        const size_t m = shape[first].first, n = shape[first].second, k = std::min(m, n);
+        std::vector<size_t> members;
+        for (size_t i = first; i < count; ++i)
+            if (!done[i] && shape[i] == shape[first]) members.push_back(i);
+        const size_t batch = members.size();
+        xrs::DevBuf A(h, batch * m * n * 8), U(h, batch * m * k * 8), S(h, batch * k * 8), Vt(h, batch * k * n * 8);
+        std::vector<double> s(batch * k);
+        for (size_t b = 0; b < batch; ++b) {
+            const double* src = _inputs[members[b]].device_data();
+            guard([&] { XRS_HIP(hipMemcpyAsync(A.d() + b * m * n, src, m * n * 8, hipMemcpyDeviceToDevice, h->stream)); });
+        }
+        guard([&] {
+            xrs::svd_batched(h, A.d(), batch, m, n, U.d(), S.d(), Vt.d(), nullptr);
+            XRS_HIP(hipMemcpyAsync(s.data(), S.d(), batch * k * 8, hipMemcpyDeviceToHost, h->stream));
+            XRS_HIP(hipStreamSynchronize(h->stream));
+        });
+        for (size_t b = 0; b < batch; ++b) {
+            const size_t i = members[b];
+            svd_outputs(Us[i], Ss[i], Vts[i], _inputs[i], _splitPos, _maxRank, _eps, m, n, U.d() + b * m * k, Vt.d() + b * k * n,
+                        s.data() + b * k);
+            done[i] = true;
+        }
+    }
+    _U = std::move(Us);
+    _S = std::move(Ss);
+    _Vt = std::move(Vts);
 }
 
 void calculate_qr(Tensor& _Q, Tensor& _R, Tensor _input, const size_t _splitPos) {

@@ -227,6 +227,14 @@ PYBIND11_MODULE(xerus, m) {
         calculate_svd(U, S, Vt, _A, _split, _maxRank, _eps);
         return py::make_tuple(U, S, Vt);
     }, py::arg("A"), py::arg("splitPos"), py::arg("maxRank") = 0, py::arg("eps") = EPSILON);
+    // calculate_svd of every tensor of a list: one batched device call per unfolding shape; a list of (U, S, Vt)
+    m.def("calculate_svd_batched", [](const std::vector<Tensor>& _As, size_t _split, size_t _maxRank, value_t _eps) {
+        std::vector<Tensor> U, S, Vt;
+        calculate_svd(U, S, Vt, _As, _split, _maxRank, _eps);
+        py::list out;
+        for (size_t i = 0; i < U.size(); ++i) out.append(py::make_tuple(U[i], S[i], Vt[i]));
+        return out;
+    }, py::arg("As"), py::arg("splitPos"), py::arg("maxRank") = 0, py::arg("eps") = EPSILON);
     m.def("calculate_qr", [](const Tensor& _A, size_t _split) {
         Tensor Q, R;
         calculate_qr(Q, R, _A, _split);

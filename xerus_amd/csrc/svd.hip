@@ -18,6 +18,7 @@
 #include <cmath>
 #include <cstdlib>
 
+#include "jacobi_dev.hpp"
 #include "smallla.hpp"
 
 namespace xrs {
@@ -26,78 +27,6 @@ namespace {
 
 constexpr int SV_LDS = 18432;   // doubles (144 KiB)
 constexpr int SV_MAXP = 512;
-
-// DPP move of a double (two 32-bit moves); CTRL is a DPP16 control word whose every lane has a valid
-// source (row rotations / mirrors / quad permutations), so no "old" value is needed (mov_dpp: no
-// zero-initialised destination, which update_dpp(0, ...) costs two extra moves per double)
-template <int CTRL>
-__device__ __forceinline__ double dpp(double v) {
-    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-
-
-// Sum over a group of G (8, 16 or 32) consecutive lanes. Every lane of the group ends with the same bits:
-// each step adds two values that are equal up to the order of operands of commutative adds.
-//   G = 16: row_ror 8, 4, 2, 1 (rotations of an increasingly periodic sequence)
-//   G = 8:  row_half_mirror (i <-> 7-i), quad_perm [2,3,0,1] (i <-> i^2), quad_perm [1,0,3,2] (i <-> i^1)
-template <int G>
-__device__ __forceinline__ double gsum(double v) {
-    if constexpr (G == 16 || G == 32) {
-        v += dpp<0x128>(v);
-        v += dpp<0x124>(v);
-        v += dpp<0x122>(v);
-        v += dpp<0x121>(v);
-        if constexpr (G == 32) {   // the two DPP rows of the group: the two results of v_permlane16_swap(v, v)
-            // are {own, partner} on every lane, so their sum is the pair sum without a per-lane select
-            const auto lo = __builtin_amdgcn_permlane16_swap(__double2loint(v), __double2loint(v), false, false);
-            const auto hi = __builtin_amdgcn_permlane16_swap(__double2hiint(v), __double2hiint(v), false, false);
-            v = __hiloint2double(hi[0], lo[0]) + __hiloint2double(hi[1], lo[1]);
-        }
-    } else {
-        static_assert(G == 8, "groups of 8 or 16 lanes");
-        v += dpp<0x141>(v);
-        v += dpp<0x4E>(v);
-        v += dpp<0xB1>(v);
-    }
-    return v;
-}
-
-// 1/x and sqrt(x) to ~1 ulp from the hardware estimates + Newton steps (rotation parameters only need
-// to be mutually consistent; no IEEE division / square-root sequences in the per-round critical path)
-__device__ __forceinline__ double frcp(double x) {
-    double r = __builtin_amdgcn_rcp(x);
-    double e = fma(-x, r, 1.0);
-    r = fma(r, e, r);
-    e = fma(-x, r, 1.0);
-    return fma(r, e, r);
-}
-__device__ __forceinline__ double fsqrt(double x) {   // x > 0
-    double y = __builtin_amdgcn_rsq(x);
-    double h = 0.5 * y;
-    double g = x * y;
-    double r = fma(-g, h, 0.5);
-    g = fma(g, r, g);
-    h = fma(h, r, h);
-    r = fma(-g, h, 0.5);
-    return fma(g, r, g);
-}
-
-// Jacobi rotation zeroing the (i,j) entry of [[a c][c b]]: t = tan(theta) = sign(b - a) 2c /
-// (|b - a| + sqrt((b - a)^2 + 4 c^2)) (the smaller root), c = 1/sqrt(1+t^2), s = t c, tau = s / (1 + c)
-__device__ __forceinline__ void rotation(double a, double b, double c, double& s, double& tau, double& tn) {
-    const double dd = b - a;
-    const double hh = fsqrt(fma(dd, dd, 4.0 * c * c));
-    tn = copysign(2.0, dd) * c * frcp(fabs(dd) + hh);
-    const double qq = fsqrt(fma(tn, tn, 1.0));   // 1 / cos
-    s = tn * frcp(qq);
-    tau = tn * frcp(1.0 + qq);   // = s / (1 + cos); Rutishauser: x' = x - s (y + tau x), y' = y + s (x - tau y)
-}
-__device__ __forceinline__ void rotation(double a, double b, double c, double& s, double& tau) {
-    double tn;
-    rotation(a, b, c, s, tau, tn);
-}
 
 // Early stop of the block kernel (flags & 2, the truncation sweeps): a sweep whose rotations all had
 // |cos| = |w_i . w_j| / (||w_i|| ||w_j||) <= 1e-7 ends the iteration. Cyclic Jacobi converges quadratically,
