@@ -16,6 +16,7 @@
 #include "xerus/measurments.h"
 #include "xerus/algorithms/adf.h"
 #include "xerus/algorithms/uqAdf.h"
+#include "xerus/algorithms/largestEntry.h"
 
 namespace xerus {
 namespace gpu {

@@ -93,6 +93,13 @@ class TTTensor {
 
     value_t frob_norm() const;
 
+    /// the entry at a row-major position over `dimensions` / at a multi-index (the reference's TTNetwork has
+    /// it through TensorNetwork::operator[], tensorNetwork.cpp:310-370); evaluated on the GPU by the forward
+    /// stack of the measurement sets; an out-of-range position throws generic_error
+    /// (host/largest_entry.cpp)
+    value_t operator[](const size_t _position) const;
+    value_t operator[](const std::vector<size_t>& _positions) const;
+
     /// fixes mode _mode to _slatePosition: the sliced core (a matrix) is contracted into its right
     /// neighbour (the left one for the last mode), as TensorNetwork::fix_mode + contract_unconnected_subnetworks
     /// (ttNetwork.cpp:432-435, 748-778, tensorNetwork.cpp:912-951)
@@ -135,6 +142,10 @@ bool approx_equal(const TTTensor& _a, const TTTensor& _b, const value_t _eps = E
 /// entrywise (Hadamard) product, rank r_A r_B (ttNetwork.cpp:1275-1309): one HBM-bound kernel per core
 /// (xrs_tt_entrywise_product); moved to A's core position when both inputs are canonical
 TTTensor entrywise_product(const TTTensor& _A, const TTTensor& _B);
+/// _A o _A in the symmetric basis, ranks r (r + 1) / 2 (an addition with no reference counterpart): the same
+/// tensor as entrywise_product(_A, _A), which keeps its Kronecker form of rank r^2. One launch writes all
+/// cores (xrs_tt_entrywise_square); a canonical input gives a result moved to the input's core position
+TTTensor entrywise_square(const TTTensor& _A);
 /// the tensor product of two TTs: components of _lhs, then of _rhs (ttNetwork.cpp:1319-1429)
 TTTensor dyadic_product(const TTTensor& _lhs, const TTTensor& _rhs);
 /// repeated dyadic_product, right to left (ttNetwork.cpp:1435-1445)
@@ -275,6 +286,8 @@ TTOperator operator*(TTOperator _op, const value_t _factor);
 TTOperator operator/(TTOperator _op, const value_t _divisor);
 inline value_t frob_norm(const TTOperator& _op) { return _op.frob_norm(); }
 TTOperator entrywise_product(const TTOperator& _A, const TTOperator& _B);
+/// the symmetric-basis square of an operator (see entrywise_square(const TTTensor&)), on its TT view
+TTOperator entrywise_square(const TTOperator& _A);
 TTOperator dyadic_product(const TTOperator& _lhs, const TTOperator& _rhs);
 TTOperator dyadic_product(const std::vector<TTOperator>& _tensors);
 

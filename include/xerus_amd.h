@@ -206,6 +206,24 @@ int xrs_tt_soft_threshold(xrs_handle_t handle, size_t d, const size_t* n, size_t
  *  to A's core position when both inputs are canonical). */
 int xrs_tt_entrywise_product(xrs_handle_t handle, size_t d, const size_t* ext, const size_t* ra, const double* const* A,
                              const size_t* rb, const double* const* B, double alpha, double** out);
+/** Entrywise square X o X of one TT in the symmetric basis (no reference counterpart; it replaces the
+ *  entrywise_product(X, X) of find_largest_entry, largestEntry.cpp:20). The Kronecker cores X_k[i] (x) X_k[i]
+ *  commute with the swap of the two factors, so the chain lives in Sym^2(R^r) on every edge; in the orthonormal
+ *  basis u_aa = e_a (x) e_a, u_ab = (e_a (x) e_b + e_b (x) e_a) / sqrt 2 (a < b) the cores represent the same tensor
+ *  with r_out[k] = r[k] (r[k] + 1) / 2 (k = 0..d) instead of r[k]^2. out[k] = (r_out[k], ext[k], r_out[k+1]), pair
+ *  index p(a, b) = a r - a (a - 1) / 2 + (b - a) for 0 <= a <= b < r, and with A = A[k], left pair (a, b), right
+ *  pair (a', b'):   a = b, a' = b':  A[a,i,a']^2 (exactly fl(x x));      a = b, a' < b':  sqrt 2 A[a,i,a'] A[a,i,b'];
+ *                   a < b, a' = b':  sqrt 2 A[a,i,a'] A[b,i,a'];         else  A[a,i,a'] A[b,i,b'] + A[a,i,b'] A[b,i,a'].
+ *  alpha is multiplied into out[0]; ext[k] as in xrs_tt_entrywise_product. One launch writes all cores (up to 64
+ *  per launch) into new buffers of the handle's pool (release with xrs_free; released on failure). r[k] < 65536.
+ *  No canonicalisation. Enqueued only. */
+int xrs_tt_entrywise_square(xrs_handle_t handle, size_t d, const size_t* ext, const size_t* r, const double* const* A,
+                            double alpha, double** out, size_t* r_out);
+/** For a TT whose ranks are all 1 (cores of ext[k] doubles): pos[k] (host) = the first index of the entry of
+ *  largest modulus of core k, the strict > scan of find_largest_entry's rank-one branch (largestEntry.cpp:45-50);
+ *  NaN entries never win (an all-NaN core gives 0). One launch (a workgroup per core), one device-to-host copy
+ *  of the d indices. d <= 2048. Synchronises. */
+int xrs_tt_rank_one_argmax(xrs_handle_t handle, size_t d, const size_t* ext, const double* const* cores, size_t* pos);
 /** TTOperator application, the core-wise contraction of a TTStack (ttStack.cpp:197-309, built by
  *  TTNetwork<true>::specialized_contraction_f, ttNetwork.cpp:886-967). Operator A: cores
  *  (ra[k], n[k], m[k], ra[k+1]). With p == NULL, B is a TTTensor with cores (rb[k], m[k], rb[k+1]) and

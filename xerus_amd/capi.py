@@ -60,6 +60,9 @@ SIGNATURES = {
     "xrs_sym_tridiag": (C.c_int, [_DP, _DP, _DP, _DP, _SZ]),
     "xrs_tt_entrywise_product": (C.c_int, [_DP, _SZ, C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(_DP), C.POINTER(_SZ), C.POINTER(_DP),
                                            C.c_double, C.POINTER(_DP)]),
+    "xrs_tt_entrywise_square": (C.c_int, [_DP, _SZ, C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(_DP), C.c_double, C.POINTER(_DP),
+                                          C.POINTER(_SZ)]),
+    "xrs_tt_rank_one_argmax": (C.c_int, [_DP, _SZ, C.POINTER(_SZ), C.POINTER(_DP), C.POINTER(_SZ)]),
     "xrs_tt_operator_apply": (C.c_int, [_DP, _SZ, C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(_DP),
                                         C.POINTER(_SZ), C.POINTER(_DP), C.c_int, C.POINTER(_DP)]),
     "xrs_tt_move_core": (C.c_int, [_DP, _SZ, C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(_DP), C.c_int, _SZ, _SZ, C.c_int]),
@@ -667,6 +670,26 @@ class TTDevice:
         _, ry, yc = other._arrays()
         _check("xrs_tt_dot_async", self.handle.lib.xrs_tt_dot_async(self.handle.h, self.order, n, rx, xc, ry, yc))
         return DotFuture(self.handle)
+
+    def entrywise_square(self, alpha: float = 1.0) -> "TTDevice":
+        """self o self in the symmetric basis (xrs_tt_entrywise_square): a new TTDevice with ranks r (r + 1) / 2,
+        alpha multiplied into its first core; not canonical."""
+        d = self.order
+        n, r, cores = self._arrays()
+        out, r_out = (_DP * d)(), (_SZ * (d + 1))()
+        _check("xrs_tt_entrywise_square", self.handle.lib.xrs_tt_entrywise_square(self.handle.h, d, n, r, cores, float(alpha),
+                                                                                  out, r_out))
+        return TTDevice(self.handle, self.dims, list(r_out), [p or 0 for p in out])
+
+    def rank_one_argmax(self) -> list:
+        """Per core of a rank-one TT the first index of the entry of largest modulus (xrs_tt_rank_one_argmax)."""
+        if any(x != 1 for x in self.r):
+            raise ValueError(f"rank_one_argmax needs ranks 1, got {self.r}")
+        d = self.order
+        n, _, cores = self._arrays()
+        pos = (_SZ * d)()
+        _check("xrs_tt_rank_one_argmax", self.handle.lib.xrs_tt_rank_one_argmax(self.handle.h, d, n, cores, pos))
+        return [int(p) for p in pos]
 
     def frob_norm(self) -> float:
         if self.canonicalized:

@@ -352,6 +352,8 @@ PYBIND11_MODULE(xerus, m) {
         .def("soft_threshold", py::overload_cast<const double, const bool>(&TTTensor::soft_threshold), py::arg("tau"),
              py::arg("preventZero") = false)
         .def("frob_norm", &TTTensor::frob_norm)
+        .def("__getitem__", [](const TTTensor& _t, const size_t _position) { return _t[_position]; })
+        .def("__getitem__", [](const TTTensor& _t, const std::vector<size_t>& _positions) { return _t[_positions]; })
         .def("exceeds_maximal_ranks", &TTTensor::exceeds_maximal_ranks)
         .def("__call__", [](TTTensor& _t, py::args _a) { return _t(to_indices(_a)); }, py::keep_alive<0, 1>())
         .def(py::self + py::self)
@@ -366,6 +368,12 @@ PYBIND11_MODULE(xerus, m) {
     m.def("entrywise_product", py::overload_cast<const Tensor&, const Tensor&>(&entrywise_product));
     m.def("entrywise_product", py::overload_cast<const TTTensor&, const TTTensor&>(&entrywise_product));
     m.def("entrywise_product", py::overload_cast<const TTOperator&, const TTOperator&>(&entrywise_product));
+    m.def("entrywise_square", py::overload_cast<const TTTensor&>(&entrywise_square));
+    m.def("entrywise_square", py::overload_cast<const TTOperator&>(&entrywise_square));
+    m.def("find_largest_entry", py::overload_cast<const TTTensor&, const double, const value_t>(&find_largest_entry), py::arg("x"),
+          py::arg("accuracy"), py::arg("lowerBound") = 0.0);
+    m.def("find_largest_entry", py::overload_cast<const TTOperator&, const double, const value_t>(&find_largest_entry), py::arg("x"),
+          py::arg("accuracy"), py::arg("lowerBound") = 0.0);
     m.def("dyadic_product", py::overload_cast<const TTTensor&, const TTTensor&>(&dyadic_product));
     m.def("dyadic_product", py::overload_cast<const std::vector<TTTensor>&>(&dyadic_product));
     m.def("dyadic_product", py::overload_cast<const TTOperator&, const TTOperator&>(&dyadic_product));
