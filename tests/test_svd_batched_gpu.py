@@ -12,7 +12,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(2, 2), (1, 7), (7, 1), (5, 3), (3, 5), (16, 16), (17, 33), (33, 17), (64, 64), (32, 256)]
+SHAPES = [(2, 2), (1, 7), (7, 1), (5, 3), (3, 5), (16, 16), (17, 33), (33, 17), (64, 64), (32, 256), (40, 100), (100, 40)]
 BATCHES = [1, 3, 37]
 
 

@@ -387,6 +387,20 @@ static auto range_controlled(xrs_handle_t h, const double* A, size_t count, Run 
     return r;
 }
 
+// The same rule for the SVD, eigenvalue and Jacobi entry points, whose kernels square the entries (unscaled,
+// 1e150-sized entries overflowed the dots): max |A| is read first (range_exponent: one synchronisation) and run()
+// gets A, or the copy A 2^-ex of an out-of-range A. Returns ex (0: unscaled); the caller scales the values back
+// by 2^ex. The power of two is applied by ldexp on the entries: 2^-ex itself is not representable for a
+// subnormal max |A| (ex < -1023).
+template <class Run>
+static int range_scaled(xrs_handle_t h, const double* A, size_t count, Run run) {
+    const int ex = range_exponent(h, A, count);
+    DevBuf As(h, ex != 0 ? count * 8 : 0);
+    if (ex != 0) ldexp_copy(h, As.d(), A, -ex, count);
+    run(ex != 0 ? As.d() : A);
+    return ex;
+}
+
 size_t qc(xrs_handle_t h, const double* A, size_t m, size_t n, double* Q, double* C) {
     XRS_REQUIRE(m > 0 && n > 0, "Dimension m and n must be larger than zero");
     return range_controlled(h, A, m * n, [&](const double* X) { return qc_core(h, X, m, n, Q, C); },
@@ -468,18 +482,9 @@ void svd(xrs_handle_t h, const double* A, size_t m, size_t n, double* U, double*
     // square 16..128: the bidiagonal route on A itself (scale-safe by construction)
     if (m == n && n >= 16 && n <= 128 && svd_bidiag_mode() != 0 && try_bidiag(h, A, n, U, S, Vt)) return;
     // range control, dgesdd's dlascl of A into [smlnum, bignum] (here by an exact power of two, to max |A| ~ 1):
-    // the Gram-based preconditioning and the Jacobi dots square the entries (unscaled, 1e150-sized entries
-    // overflowed them). The power of two is applied by ldexp on the entries: 2^-ex itself is not representable
-    // for a subnormal max |A| (ex < -1023).
-    const int ex = range_exponent(h, A, m * n);
-    if (ex != 0) {
-        DevBuf As(h, m * n * 8);
-        ldexp_copy(h, As.d(), A, -ex, m * n);
-        svd_core(h, As.d(), m, n, U, S, Vt);
-        ldexp_copy(h, S, S, ex, std::min(m, n));
-        return;
-    }
-    svd_core(h, A, m, n, U, S, Vt);
+    // the Gram-based preconditioning and the Jacobi dots square the entries
+    const int ex = range_scaled(h, A, m * n, [&](const double* X) { svd_core(h, X, m, n, U, S, Vt); });
+    ldexp_copy(h, S, S, ex, std::min(m, n));   // (nothing for ex = 0)
 }
 
 static void svd_core(xrs_handle_t h, const double* A, size_t m, size_t n, double* U, double* S, double* Vt) {
@@ -561,15 +566,12 @@ int xrs_sym_eig_top(xrs_handle_t h, double* lam, double* Ut, int* status, const 
         XRS_REQUIRE(h && lam && Ut && status && A, "null argument");
         XRS_REQUIRE(n >= 2 && n <= 256 && kk >= 1 && kk <= n, "xrs_sym_eig_top: need 2 <= n <= 256 and 1 <= kk <= n");
         fence_readers(h);
-        DevBuf st(h, 64), As;
+        DevBuf st(h, 64);
         XRS_HIP(hipMemsetAsync(st.d(), 0, 64, h->stream));
         // (range control: the tridiagonalisation's reflector norms and the Sturm counts square the entries)
-        const int ex = range_exponent(h, A, n * n);
-        if (ex != 0) {
-            As = DevBuf(h, n * n * 8);
-            ldexp_copy(h, As.d(), A, -ex, n * n);
-        }
-        sym_eig_top(h, ex != 0 ? As.d() : A, int(n), int(n), int(kk), lam, nullptr, Ut, int(n), st.as<int>());
+        const int ex = range_scaled(h, A, n * n, [&](const double* X) {
+            sym_eig_top(h, X, int(n), int(n), int(kk), lam, nullptr, Ut, int(n), st.as<int>());
+        });
         ldexp_copy(h, lam, lam, ex, kk);
         read_status(h, st.as<int>(), 1, status);
     });
@@ -590,14 +592,11 @@ int xrs_svd_rows_vt(xrs_handle_t h, double* S, double* Vt, int* sweeps, const do
         XRS_REQUIRE(h && S && Vt && A && sweeps, "null argument");
         XRS_REQUIRE(p >= 1 && p <= q && q <= 1024 && (kernel != 1 || p <= 512),
                     "xrs_svd_rows_vt: need 1 <= p <= q <= 1024 (kernel 1: p <= 512)");
-        DevBuf st(h, 64), As;
+        DevBuf st(h, 64);
         XRS_HIP(hipMemsetAsync(st.d(), 0, 64, h->stream));
-        const int ex = range_exponent(h, A, p * q);   // (range control: the Jacobi dots square the entries)
-        if (ex != 0) {
-            As = DevBuf(h, p * q * 8);
-            ldexp_copy(h, As.d(), A, -ex, p * q);
-        }
-        jacobi_vt(h, ex != 0 ? As.d() : A, int(q), false, int(p), int(q), S, Vt, int(q), st.as<int>(), 40, kernel, stamps_enabled("svd"));
+        const int ex = range_scaled(h, A, p * q, [&](const double* X) {   // (the Jacobi dots square the entries)
+            jacobi_vt(h, X, int(q), false, int(p), int(q), S, Vt, int(q), st.as<int>(), 40, kernel, stamps_enabled("svd"));
+        });
         ldexp_copy(h, S, S, ex, p);
         int sts[9];
         read_status(h, st.as<int>(), 9, sts);

@@ -1305,33 +1305,23 @@ size_t qrcp(xrs_handle_t h, const double* A, size_t m, size_t n, double* Q, doub
 
 void jacobi_svd_rows(xrs_handle_t h, const double* W, int p, int q, double* U, double* S, double* Vt) {
     XRS_REQUIRE(p >= 1 && p <= PMAX && p <= q, "jacobi_svd_rows: need 1 <= p <= min(q, 512)");
-    if (jacobi_usv_fits(p, q)) {
-        // multi-workgroup block Jacobi with the rotations accumulated (svd.hip); non-convergence is a
-        // warning, as the reference's dgesdd failure (blasLapackWrapper.cpp:216-224)
-        DevBuf st(h, 64);
-        jacobi_usv(h, W, q, false, p, q, U, p, S, Vt, q, st.as<int>(), 60);
-        int sweeps = 0;
-        read_status(h, st.as<int>(), 1, &sweeps);
-        if (sweeps != -2) {
-            if (sweeps < 0)
-                std::fprintf(stderr, "[xerus_amd warning] SVD failed: one-sided Jacobi of a %d x %d matrix did not converge (status %d)\n",
-                             p, q, sweeps);
-            return;
-        }
-        // -2: a bounded grid-barrier poll timed out (a workgroup was not scheduled), so the multi-workgroup
-        // result is not valid at all -- not a convergence failure: redo the SVD in one workgroup below
-        std::fprintf(stderr, "[xerus_amd warning] multi-workgroup Jacobi barrier timed out (%d x %d); rerun in one workgroup\n", p, q);
-    }
-    DevBuf Wc(h, size_t(p) * q * 8), J(h, size_t(p) * p * 8), st(h, 64);
-    XRS_HIP(hipMemcpyAsync(Wc.d(), W, size_t(p) * q * 8, hipMemcpyDeviceToDevice, h->stream));
-    {
+    DevBuf st(h, 64);
+    // one workgroup, no grid barrier: k_jacobi + k_svd_finish on a copy of W
+    auto one_workgroup = [&](int) {
+        DevBuf Wc(h, size_t(p) * q * 8), J(h, size_t(p) * p * 8);
+        XRS_HIP(hipMemcpyAsync(Wc.d(), W, size_t(p) * q * 8, hipMemcpyDeviceToDevice, h->stream));
         KernelTimer timer(h, XRS_KFAM_SVD, 8.0 * double(p) * p * (p + q), 0.0);
         hipLaunchKernelGGL(k_jacobi, dim3(1), dim3(1024), 0, h->stream, Wc.d(), p, q, J.d(), 60, 4.0 * 2.220446049250313e-16,
                            st.as<int>());
         check_launch("k_jacobi");
         hipLaunchKernelGGL(k_svd_finish, dim3(1), dim3(1024), 0, h->stream, Wc.d(), p, q, J.d(), U, S, Vt);
         check_launch("k_svd_finish");
-    }
+    };
+    if (!jacobi_usv_fits(p, q)) return one_workgroup(1);
+    // multi-workgroup block Jacobi with the rotations accumulated (svd.hip); a timed-out grid barrier (-2)
+    // is rerun in one workgroup by jacobi_settle (k_jacobi's status is never -2: one rerun settles it)
+    jacobi_usv(h, W, q, false, p, q, U, p, S, Vt, q, st.as<int>(), 60);
+    jacobi_settle(h, st.as<int>(), p, q, one_workgroup);
 }
 
 }  // namespace xrs

@@ -1,4 +1,4 @@
-// Launch wrappers of the small dense kernels (smallla.hip) and the factorisation drivers (linalg.cpp).
+// Launch wrappers of the small dense kernels (smallla.hip) and the factorisation drivers (linalg.hip).
 #pragma once
 #include <functional>
 #include <vector>
@@ -65,6 +65,9 @@ bool jacobi_vt_fits_lds(int p, int q);
 // Full SVD of the rows of W (p x q, p <= q, 32 ceil(q/32) + p <= 1024) by the block Jacobi kernel with
 // the rotations accumulated (svd.hip): W = U diag(S) Vt, U p x p orthogonal (row stride ldu), S
 // descending, Vt p x q (orthonormal rows for S > 0). Status as jacobi_vt. Enqueued only.
+bool jacobi_usv_fits(int p, int q);
+void jacobi_usv(xrs_handle_t h, const double* W, int ldw, bool trans, int p, int q, double* U, int ldu, double* S, double* Vt, int ldvt,
+                int* status_dev, int max_sweeps = 40, bool early = false);
 // Eigenpairs of the kk largest eigenvalues of a symmetric n x n matrix A (lower triangle read, 2 <= n <= 256):
 // Householder tridiagonalisation (one workgroup, register-resident), multisection + inverse iteration per
 // eigenvalue, back-transformation (syev.hip). lam (kk, optional) descending, S = sqrt(max(lam, 0))
@@ -80,9 +83,6 @@ void sym_tridiag(xrs_handle_t h, const double* A, int lda, int n, double* d, dou
 // svd_bidiag_mode: XRS_SVD_BIDIAG (0 off, 1 on with the Jacobi fallback (default), 2 strict: failure throws).
 int svd_bidiag_mode();
 bool svd_bidiag(xrs_handle_t h, const double* A, int n, double* U, double* S, double* Vt, double* diag = nullptr);
-bool jacobi_usv_fits(int p, int q);
-void jacobi_usv(xrs_handle_t h, const double* W, int ldw, bool trans, int p, int q, double* U, int ldu, double* S, double* Vt, int ldvt,
-                int* status_dev, int max_sweeps = 40, bool early = false);
 // Right singular vectors (rows of Vt, g x g) and S of a triangular g x g factor F: lower (L of B = L Q) by
 // accumulated rotations on the rows of F^T, upper (R of B = Q R) on the rows of F. Enqueued only.
 // early: the block kernel's early stop (svd.hip kEarlyCos2: no confirming sweep after one whose rotations

@@ -15,6 +15,9 @@
 // in Rutishauser's form x' = x - s (y + tau x), y' = y + s (x - tau y) (O(u s) perturbation for
 // nearly-identity rotations). 64 groups: up to 64 pairs per round in flight, one barrier per round.
 // Convergence: no pair with |w_i . w_j| > tol ||w_i|| ||w_j||, tol = sqrt(q) u (dgesvj's criterion).
+// The pairing, the sweep loop with this stopping rule and the ranking of the row norms are jacobi_dev.hpp's
+// (circle_pair, jacobi_sweeps, jacobi_rank_rows), shared with svd_batched.hip; this file has the rotation of
+// a row pair (rotate_regs / rotate_pair), the load and the write-out.
 #include <cmath>
 #include <cstdlib>
 
@@ -48,10 +51,7 @@ __device__ __forceinline__ void store_row_full(const double (&x)[E], double* __r
     for (int e = 0; e < E; ++e) w[l + e * G] = x[e];
 }
 
-// One Jacobi step on the row pair (wi, wj) of length q by a group of G lanes (lane l): orthogonalise the
-// rows if |wi . wj| > tol ||wi|| ||wj||; true if rotated. E > 0: q <= E * G, the lane's elements are held
-// in registers (all loads issued before any use); E = 0: any q, streamed.
-// The register core: the lane's E elements of each row (zero beyond q, which rotations keep zero)
+// The register core of rotate_pair below: the lane's E elements of each row (zero beyond q, which rotations keep zero)
 // (the inner products run over the first ew elements: the rest may carry accumulated rotations)
 template <int G, int E>
 __device__ __forceinline__ bool rotate_regs(double (&x)[E], double (&y)[E], double tol2, int ew = E, bool* big = nullptr) {
@@ -134,7 +134,8 @@ __device__ __forceinline__ bool rotate_pair(double* __restrict__ wi, double* __r
     }
 }
 
-// player at position x of round `round` (circle method, P players, position 0 fixed)
+// player at position x of round `round` (circle method, P players, position 0 fixed): circle_pair's map, as the
+// block kernel's within-block rounds spell it (P = BR is a constant there)
 __device__ __forceinline__ int player(int x, int round, int P) { return x == 0 ? 0 : 1 + (x - 1 + round) % (P - 1); }
 
 // W (ldw) is the working copy (LDS or global scratch); Win (row stride ldin, or transposed) the input.
@@ -143,8 +144,7 @@ template <int G, int NT, int E>
 __device__ void jacobi_rows_body(double* __restrict__ W, int ldw, const double* __restrict__ Win, int ldin, bool trans, int p, int q,
                                  int max_sweeps, double* __restrict__ S, double* __restrict__ Vt, int ldvt,
                                  int* __restrict__ status) {
-    constexpr int GROUPS = NT / G;
-    const int tid = threadIdx.x, g = tid / G, l = tid % G;
+    const int tid = threadIdx.x;
     __shared__ int rotated;
     __shared__ double sn[SV_MAXP];
     __shared__ int rk[SV_MAXP];
@@ -160,54 +160,20 @@ __device__ void jacobi_rows_body(double* __restrict__ W, int ldw, const double* 
         }
     }
     __syncthreads();
-    const int P = (p + 1) & ~1;
-    const double tol = sqrt(double(q)) * 1.1102230246251565e-16;
+    const double tol = jacobi_tol(q);
     const double tol2 = tol * tol;
-    int sweep = 0;
-    bool converged = false;
-    for (; sweep < max_sweeps && !converged; ++sweep) {
-        if (tid == 0) rotated = 0;
-        __syncthreads();
-        for (int round = 0; round < P - 1; ++round) {
-            for (int t = g; t < P / 2; t += GROUPS) {
-                int i = 0, j;   // players at positions t and P-1-t (player() without the integer divisions)
-                if (t > 0) {
-                    i = t + round;
-                    i = i >= P ? i - (P - 1) : i;
-                }
-                j = P - 1 - t + round;
-                j = j >= P ? j - (P - 1) : j;
-                if (i >= p || j >= p) continue;
-                if (rotate_pair<G, E>(W + size_t(i) * ldw, W + size_t(j) * ldw, q, l, tol2) && l == 0) rotated = 1;
-            }
-            __syncthreads();
-        }
-        converged = rotated == 0;
-        __syncthreads();
-    }
-    // singular values = row norms, ranked descending (ties by index: a stable order)
-    for (int i = g; i < p; i += GROUPS) {
-        const double* wi = W + size_t(i) * ldw;
-        double a = 0.0;
-        for (int k = l; k < q; k += G) a = fma(wi[k], wi[k], a);
-        a = gsum<G>(a);
-        if (l == 0) sn[i] = sqrt(a);
-    }
-    __syncthreads();
-    for (int i = tid; i < p; i += NT) {
-        const double si = sn[i];
-        int r = 0;
-        for (int j2 = 0; j2 < p; ++j2) r += (sn[j2] > si) || (sn[j2] == si && j2 < i);
-        rk[i] = r;
-        S[r] = si;
-    }
-    __syncthreads();
+    const JacobiSweeps done = jacobi_sweeps<G>(p, NT, max_sweeps, &rotated, [&](int i, int j, int l) {
+        return rotate_pair<G, E>(W + size_t(i) * ldw, W + size_t(j) * ldw, q, l, tol2);
+    });
+    // singular values = row norms, ranked descending
+    jacobi_rank_rows<G>(W, size_t(ldw), p, q, NT, sn, rk);
+    for (int i = tid; i < p; i += NT) S[rk[i]] = sn[i];
     for (int e = tid; e < p * q; e += NT) {
         const int i = e / q, k = e - i * q;
         const double s = sn[i];
         Vt[size_t(rk[i]) * ldvt + k] = s > 0.0 ? W[size_t(i) * ldw + k] / s : 0.0;
     }
-    if (tid == 0) status[0] = converged ? sweep : -1;
+    if (tid == 0) status[0] = done.converged ? done.sweeps : -1;
 }
 
 // LDS-resident: 512 threads, 8 lanes per pair (64 pairs in flight, two waves per SIMD)
@@ -328,7 +294,7 @@ __global__ void __launch_bounds__(BR * G) k_jacobi_vt_blocks(const double* __res
     // data, [w (ew * G) | j (p)]; dots and norms run over the first ew register elements only
     const int ew = ACC ? (q + G - 1) / G : E;
     const int qpad = ew * G;
-    const double tol = sqrt(double(q)) * 1.1102230246251565e-16;
+    const double tol = jacobi_tol(q);
     const double tol2 = tol * tol;
     if (tid == 0) err = 0;
     // block id at tournament position x in outer round t
@@ -561,6 +527,19 @@ void launch_blocks(xrs_handle_t h, const double* W, int ldw, bool trans, int p, 
     check_launch("k_jacobi_vt_blocks");
 }
 
+// the register tiling E * 32 columns: the narrowest that holds a row of `width` doubles (padding costs FMAs and
+// LDS traffic); rows of more than 512: blocks of 8 rows (2 x 8 x 1024 doubles of LDS)
+template <bool ACC, class... Args>
+void launch_blocks_fit(int width, Args... args) {
+    if constexpr (!ACC) {
+        if (width <= 64) return launch_blocks<16, 32, 2, false>(args...);
+    }
+    if (width <= 128) launch_blocks<16, 32, 4, ACC>(args...);
+    else if (width <= 256) launch_blocks<16, 32, 8, ACC>(args...);
+    else if (width <= 512) launch_blocks<16, 32, 16, ACC>(args...);
+    else launch_blocks<8, 32, 32, ACC>(args...);
+}
+
 }  // namespace
 
 void jacobi_vt(xrs_handle_t h, const double* W, int ldw, bool trans, int p, int q, double* S, double* Vt, int ldvt,
@@ -574,14 +553,8 @@ void jacobi_vt(xrs_handle_t h, const double* W, int ldw, bool trans, int p, int 
     constexpr int block_min = 32;
     const bool blocks_ok = q <= 2 * SVB_QMAX;
     XRS_REQUIRE(kernel != 2 || blocks_ok, "jacobi_vt: the block kernel needs q <= 1024");
-    if (q > SVB_QMAX) {   // rows of up to 1024 columns: blocks of 8 rows (2 x 8 x 1024 doubles of LDS)
-        launch_blocks<8, 32, 32, false>(h, W, ldw, trans, p, q, S, Vt, ldvt, nullptr, 0, status_dev, max_sweeps, stamps, early);
-    } else if (blocks_ok && (kernel == 2 || (kernel == 0 && p >= block_min))) {
-        // register tiling E * 32 columns: the narrowest that holds q (padding costs FMAs and LDS traffic)
-        if (q <= 64) launch_blocks<16, 32, 2, false>(h, W, ldw, trans, p, q, S, Vt, ldvt, nullptr, 0, status_dev, max_sweeps, stamps, early);
-        else if (q <= 128) launch_blocks<16, 32, 4, false>(h, W, ldw, trans, p, q, S, Vt, ldvt, nullptr, 0, status_dev, max_sweeps, stamps, early);
-        else if (q <= 256) launch_blocks<16, 32, 8, false>(h, W, ldw, trans, p, q, S, Vt, ldvt, nullptr, 0, status_dev, max_sweeps, stamps, early);
-        else launch_blocks<16, 32, 16, false>(h, W, ldw, trans, p, q, S, Vt, ldvt, nullptr, 0, status_dev, max_sweeps, stamps, early);
+    if (q > SVB_QMAX || (blocks_ok && (kernel == 2 || (kernel == 0 && p >= block_min)))) {
+        launch_blocks_fit<false>(q, h, W, ldw, trans, p, q, S, Vt, ldvt, nullptr, 0, status_dev, max_sweeps, stamps, early);
     } else if (jacobi_vt_fits_lds(p, q)) {
         hipLaunchKernelGGL(k_jacobi_vt_lds, dim3(1), dim3(SVL_THREADS), 0, h->stream, W, ldw, int(trans), p, q, max_sweeps, S, Vt,
                            ldvt, status_dev);
@@ -601,10 +574,7 @@ void jacobi_usv(xrs_handle_t h, const double* W, int ldw, bool trans, int p, int
     XRS_REQUIRE(jacobi_usv_fits(p, q), "jacobi_usv: need p <= q and 32 ceil(q / 32) + p <= 1024");
     KernelTimer timer(h, XRS_KFAM_SVD, 3.5 * double(p) * p * (q + p) * 6.0, 16.0 * double(p) * (q + p));
     const int width = 32 * ((q + 31) / 32) + p;
-    if (width <= 128) launch_blocks<16, 32, 4, true>(h, W, ldw, trans, p, q, S, Vt, ldvt, U, ldu, status_dev, max_sweeps, false, early);
-    else if (width <= 256) launch_blocks<16, 32, 8, true>(h, W, ldw, trans, p, q, S, Vt, ldvt, U, ldu, status_dev, max_sweeps, false, early);
-    else if (width <= 512) launch_blocks<16, 32, 16, true>(h, W, ldw, trans, p, q, S, Vt, ldvt, U, ldu, status_dev, max_sweeps, false, early);
-    else launch_blocks<8, 32, 32, true>(h, W, ldw, trans, p, q, S, Vt, ldvt, U, ldu, status_dev, max_sweeps, false, early);
+    launch_blocks_fit<true>(width, h, W, ldw, trans, p, q, S, Vt, ldvt, U, ldu, status_dev, max_sweeps, false, early);
 }
 
 int jacobi_settle(xrs_handle_t h, int* status_dev, int p, int q, const std::function<void(int kernel)>& rerun) {

@@ -1,6 +1,7 @@
 // Batched thin SVD: one launch factors `batch` small m x n matrices, one workgroup per matrix.
 //
-// Method (svd.hip's k_jacobi_vt_lds, per workgroup): one-sided Jacobi on the rows of the wide orientation
+// Method (that of svd.hip's k_jacobi_vt_lds, per workgroup; the pairing, the sweep loop and the ranking of the row
+// norms are the same code: jacobi_dev.hpp): one-sided Jacobi on the rows of the wide orientation
 // W (p x q, p = min(m, n) <= q = max(m, n); W = A or A^T), resident in LDS for the whole solve. Round-robin
 // pairing of the P = p rounded up to even players, a 16-lane group per pair with the lane's elements of both
 // rows in registers, DPP-butterfly dot products, Rutishauser rotations, dgesvj's stopping rule
@@ -88,8 +89,7 @@ __global__ void __launch_bounds__(SB_THREADS) k_svd_batched(const double* __rest
     double* const red = sn + p;
     int* const rk = reinterpret_cast<int*>(red + 8);
     int* const rotated = rk + p;
-    const int NT = blockDim.x, GROUPS = NT / SB_G;
-    const int tid = threadIdx.x, g = tid / SB_G, l = tid % SB_G;
+    const int NT = blockDim.x, tid = threadIdx.x;
     const size_t b = blockIdx.x;
     const double* __restrict__ Ab = A + b * size_t(m) * n;
 
@@ -122,48 +122,15 @@ __global__ void __launch_bounds__(SB_THREADS) k_svd_batched(const double* __rest
         W[i * ld + q + j] = i == j ? 1.0 : 0.0;
     }
 
-    const int P = (p + 1) & ~1;
-    const double tol = sqrt(double(q)) * SB_U;
+    const double tol = jacobi_tol(q);
     const double tol2 = tol * tol;
-    int sweep = 0;
-    bool converged = false;
-    for (; sweep < max_sweeps && !converged; ++sweep) {
-        if (tid == 0) *rotated = 0;
-        __syncthreads();
-        for (int round = 0; round < P - 1; ++round) {
-            for (int t = g; t < P / 2; t += GROUPS) {
-                int i = 0, j;   // players at positions t and P-1-t of the circle (position 0 fixed)
-                if (t > 0) {
-                    i = t + round;
-                    i = i >= P ? i - (P - 1) : i;
-                }
-                j = P - 1 - t + round;
-                j = j >= P ? j - (P - 1) : j;
-                if (i >= p || j >= p) continue;   // (odd p: the bye)
-                if (rotate_rows<E>(W + i * ld, W + j * ld, q, wt, l, tol2) && l == 0) *rotated = 1;
-            }
-            __syncthreads();
-        }
-        converged = *rotated == 0;
-        __syncthreads();
-    }
+    const JacobiSweeps done = jacobi_sweeps<SB_G>(p, NT, max_sweeps, rotated, [&](int i, int j, int l) {
+        return rotate_rows<E>(W + i * ld, W + j * ld, q, wt, l, tol2);
+    });
 
-    // singular values = row norms of the data columns, ranked descending (ties by index)
-    for (int i = g; i < p; i += GROUPS) {
-        const double* wi = W + i * ld;
-        double a = 0.0;
-        for (int k = l; k < q; k += SB_G) a = fma(wi[k], wi[k], a);
-        a = gsum<SB_G>(a);
-        if (l == 0) sn[i] = sqrt(a);
-    }
-    __syncthreads();
-    for (int i = tid; i < p; i += NT) {
-        const double si = sn[i];
-        int r = 0;
-        for (int j2 = 0; j2 < p; ++j2) r += (sn[j2] > si) || (sn[j2] == si && j2 < i);
-        rk[i] = r;
-        S[b * p + r] = ldexp(si, ex);
-    }
+    // singular values = row norms of the data columns, ranked descending
+    jacobi_rank_rows<SB_G>(W, size_t(ld), p, q, NT, sn, rk);
+    for (int i = tid; i < p; i += NT) S[b * p + rk[i]] = ldexp(sn[i], ex);
     // Certificate. The stopping rule leaves |w_i . w_j| <= tol ||w_i|| ||w_j||, tol = sqrt(q) u, unrotated:
     // each of the other p - 1 rows may keep a component of up to tol ||w_j|| <= tol s_max along the direction
     // of row i, (p - 1) tol s_max in all. A row whose norm does not exceed that sum need hold nothing else,
@@ -176,9 +143,8 @@ __global__ void __launch_bounds__(SB_THREADS) k_svd_batched(const double* __rest
             smax = sn[i] > smax ? sn[i] : smax;
         }
         const bool full = smin > double(p) * tol * smax;
-        status[b] = (converged && full) ? sweep : -1;
+        status[b] = (done.converged && full) ? done.sweeps : -1;
     }
-    __syncthreads();
     // J W = diag(sn) V: wide A = J^T diag(sn) V (U = J^T, Vt = V), tall A = V^T diag(sn) J (U = V^T, Vt = J)
     double* __restrict__ Ub = U + b * size_t(m) * p;
     double* __restrict__ Vb = Vt + b * size_t(p) * n;
