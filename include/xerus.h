@@ -17,6 +17,8 @@
 #include "xerus/algorithms/adf.h"
 #include "xerus/algorithms/uqAdf.h"
 #include "xerus/algorithms/largestEntry.h"
+#include "xerus/algorithms/randomSVD.h"
+#include "xerus/algorithms/decompositionAls.h"
 
 namespace xerus {
 namespace gpu {

@@ -387,6 +387,30 @@ int xrs_uq_stack_congruence(xrs_handle_t handle, double* Lout, const double* Lpr
  *  1 <= a <= 256, else XRS_EINVAL. Synchronises. */
 int xrs_uq_quadform(xrs_handle_t handle, double* result, const double* L, const double* V, size_t N, size_t a);
 
+/* ---------------------------------------------------------------- Gaussian sketches (algorithms/randomSVD.h:31-98) */
+/* G(seed, stream) is an infinite matrix whose entry (i, c) depends on (seed, stream, i, c) only: the words
+ * W(i, q) = Philox4x32-10 with key (seed low 32, seed high 32) and counter (q low 32, q high 32, i, stream), q = c / 4;
+ * with u1 = (w0 + 1) 2^-32, u2 = w1 2^-32: G(i, 4q) = sqrt(-2 ln u1) cos 2 pi u2, G(i, 4q + 1) the same with sin, and
+ * (w2, w3) give G(i, 4q + 2), G(i, 4q + 3) likewise -- Box-Muller in fp32 (device intrinsics), widened to fp64;
+ * |G| <= 6.66. Replaces the reference's Tensor::random(gDims, dist, randomEngine) of randomTTSVD (randomSVD.h:72-74),
+ * whose host mt19937_64 stream cannot fill a sketch matrix larger than the tensor. Rows (i < s) are below 2^32. */
+
+/** out (s x q x 4 words, device) = W(0..s-1, 0..q-1): the raw Philox words (a diagnostic for bit-exact tests). */
+int xrs_philox_words(xrs_handle_t handle, uint32_t* out, size_t s, size_t q, uint64_t seed, uint32_t stream);
+/** G (s x m, row-major) = the leading block of G(seed, stream). */
+int xrs_gaussian_matrix(xrs_handle_t handle, double* G, size_t s, size_t m, uint64_t seed, uint32_t stream);
+/** Y (s x n) = G[0:s, 0:m] * A (m x n) (replaces contract(a, g, false, b, false, j - 1), randomSVD.h:75).
+ *  route: 0 auto, XRS_SKETCH_FUSED (G is generated in registers inside the product and never stored; A is read
+ *  once; s <= 80, else XRS_EINVAL), XRS_SKETCH_MATERIALISED (xrs_gaussian_matrix into pool scratch, then xrs_gemm;
+ *  m < 2^30). Both routes use the same G; their results differ by the order of summation only, and each is
+ *  bit-reproducible from run to run (fixed-order split over m, no atomics). Y must not alias A. Enqueued only. */
+#define XRS_SKETCH_FUSED 1
+#define XRS_SKETCH_MATERIALISED 2
+int xrs_sketch_gaussian(xrs_handle_t handle, double* Y, size_t s, const double* A, size_t m, size_t n, uint64_t seed,
+                        uint32_t stream, int route);
+/** The route the handle's last xrs_sketch_gaussian took (XRS_SKETCH_*); 0 before the first. */
+int xrs_sketch_last_route(xrs_handle_t handle);
+
 /* ---------------------------------------------------------------- profiling */
 /** Kernel-duration instrumentation: while enabled, every launch of a kernel whose family id is in
  *  `family_mask` is bracketed by HIP events on the handle's stream. */

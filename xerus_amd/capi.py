@@ -103,6 +103,10 @@ SIGNATURES = {
     "xrs_uq_basis": (C.c_int, [_DP, _DP, _DP, _SZ, _SZ]),
     "xrs_uq_stack_congruence": (C.c_int, [_DP, _DP, _DP, _DP, _DP, _SZ, _SZ, _SZ, _SZ]),
     "xrs_uq_quadform": (C.c_int, [_DP, C.POINTER(C.c_double), _DP, _DP, _SZ, _SZ]),
+    "xrs_philox_words": (C.c_int, [_DP, _DP, _SZ, _SZ, C.c_uint64, C.c_uint32]),
+    "xrs_gaussian_matrix": (C.c_int, [_DP, _DP, _SZ, _SZ, C.c_uint64, C.c_uint32]),
+    "xrs_sketch_gaussian": (C.c_int, [_DP, _DP, _SZ, _DP, _SZ, _SZ, C.c_uint64, C.c_uint32, C.c_int]),
+    "xrs_sketch_last_route": (C.c_int, [_DP]),
     "xrs_prof_begin": (C.c_int, [_DP, C.c_uint32]),
     "xrs_prof_end": (C.c_int, [_DP, C.POINTER(_SZ), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                C.POINTER(C.c_double)]),
@@ -110,6 +114,8 @@ SIGNATURES = {
 
 KFAM_GEMM, KFAM_PERMUTE, KFAM_QR, KFAM_SVD, KFAM_ELEMWISE, KFAM_SPLITK = 1, 2, 4, 8, 16, 32
 ROUND_PATHS = {0: None, 1: "chain", 2: "truncate", 3: "reference", 4: "general"}
+SKETCH_AUTO, SKETCH_FUSED, SKETCH_MATERIALISED = 0, 1, 2
+SKETCH_ROUTES = {0: None, 1: "fused", 2: "materialised"}
 
 _lib = None
 
@@ -413,6 +419,50 @@ class Handle:
         _check("xrs_uq_quadform", self.lib.xrs_uq_quadform(self.h, C.byref(r), _DP(L.ptr) if L is not None else None,
                                                           _DP(V.ptr), N, a))
         return r.value
+
+    # ---- Gaussian sketches (G(seed, stream): include/xerus_amd.h)
+    @staticmethod
+    def _seed_stream(fn: str, seed: int, stream: int):
+        # the C types are uint64 / uint32: ctypes would wrap a larger value silently
+        if not 0 <= int(seed) < 2 ** 64:
+            raise XrsError(fn, -1, f"seed {seed} is not a 64-bit word")
+        if not 0 <= int(stream) < 2 ** 32:
+            raise XrsError(fn, -1, f"stream {stream} must be below 2^32")
+        return int(seed), int(stream)
+
+    def philox_words(self, s: int, q: int, seed: int, stream: int = 0) -> np.ndarray:
+        """xrs_philox_words: the raw Philox4x32-10 words W(0..s-1, 0..q-1) as a host (s, q, 4) uint32 array."""
+        seed, stream = self._seed_stream("xrs_philox_words", seed, stream)
+        legal = 0 < s <= 2 ** 32 and q > 0
+        buf = self.empty((2 * s * q,)) if legal else None   # 4 words = 2 doubles per block
+        _check("xrs_philox_words", self.lib.xrs_philox_words(self.h, _DP(buf.ptr) if legal else None, s, q, seed, stream))
+        return buf.numpy().view(np.uint32).reshape(s, q, 4)
+
+    def gaussian_matrix(self, s: int, m: int, seed: int, stream: int = 0) -> "DeviceArray":
+        """xrs_gaussian_matrix: the leading s x m block of G(seed, stream)."""
+        seed, stream = self._seed_stream("xrs_gaussian_matrix", seed, stream)
+        legal = 0 < s <= 2 ** 32 and m > 0
+        G = self.empty((s, m)) if legal else None
+        _check("xrs_gaussian_matrix", self.lib.xrs_gaussian_matrix(self.h, _DP(G.ptr) if legal else None, s, m, seed, stream))
+        return G
+
+    def sketch_gaussian(self, s: int, A: "DeviceArray", seed: int, stream: int = 0, route: int = 0, m: int | None = None,
+                        out: "DeviceArray | None" = None) -> "DeviceArray":
+        """xrs_sketch_gaussian: Y (s x n) = G[0:s, 0:m] A. route: 0 auto, 1 fused, 2 materialised. m (default: all
+        rows of A) sketches the leading m rows only; out (default: a new s x n array) receives Y in its first
+        s n elements."""
+        seed, stream = self._seed_stream("xrs_sketch_gaussian", seed, stream)
+        n = A.shape[1]
+        m = A.shape[0] if m is None else int(m)
+        legal = 0 < s <= 2 ** 32 and m > 0 and n > 0
+        Y = out if out is not None else (self.empty((s, n)) if legal else None)
+        _check("xrs_sketch_gaussian", self.lib.xrs_sketch_gaussian(self.h, _DP(Y.ptr) if Y is not None else None, s, _DP(A.ptr),
+                                                                  m, n, seed, stream, int(route)))
+        return Y
+
+    def sketch_last_route(self) -> str | None:
+        """"fused" / "materialised": the route of this handle's last sketch_gaussian."""
+        return SKETCH_ROUTES[self.lib.xrs_sketch_last_route(self.h)]
 
     def last_round_path(self) -> str | None:
         """"chain" / "truncate" / "general" / "reference": the algorithm of this handle's last TT round."""

@@ -374,6 +374,10 @@ PYBIND11_MODULE(xerus, m) {
           py::arg("accuracy"), py::arg("lowerBound") = 0.0);
     m.def("find_largest_entry", py::overload_cast<const TTOperator&, const double, const value_t>(&find_largest_entry), py::arg("x"),
           py::arg("accuracy"), py::arg("lowerBound") = 0.0);
+    m.def("randomTTSVD", &randomTTSVD, py::arg("x"), py::arg("ranks"), py::arg("oversampling"),
+          "TT approximation from Gaussian sketches (algorithms/randomSVD.h); seeded by one word of the thread's engine");
+    m.def("decomposition_als", &decomposition_als, py::arg("x"), py::arg("b"), py::arg("epsilon") = EPSILON,
+          py::arg("maxIterations") = size_t(1000), "fits the TT x (in place) to the dense tensor b (algorithms/decompositionAls.h)");
     m.def("dyadic_product", py::overload_cast<const TTTensor&, const TTTensor&>(&dyadic_product));
     m.def("dyadic_product", py::overload_cast<const std::vector<TTTensor>&>(&dyadic_product));
     m.def("dyadic_product", py::overload_cast<const TTOperator&, const TTOperator&>(&dyadic_product));

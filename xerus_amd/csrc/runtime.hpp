@@ -107,6 +107,8 @@ struct xrs_handle_s {
     int* side_tickets[kSides] = {};
     // algorithm of the last TT round (XRS_ROUND_*)
     int last_round_path = 0;
+    // route of the last xrs_sketch_gaussian (XRS_SKETCH_*)
+    int last_sketch_route = 0;
     // asynchronous TT inner product (xrs_tt_dot_async): enqueued by a worker thread on a child handle
     // whose streams are side streams 1 and 2 of this one (forked at ev_dot from the main stream), so the
     // caller's thread goes on enqueueing the next work at once; while `reader_pending`, releases of the
