@@ -188,6 +188,10 @@ class Handle:
     def free(self, ptr: int):
         _check("xrs_free", self.lib.xrs_free(self.h, _DP(ptr)))
 
+    def pool_bytes(self) -> int:
+        """Device bytes the handle's caching allocator holds (live and cached blocks): xrs_pool_bytes."""
+        return int(self.lib.xrs_pool_bytes(self.h))
+
     def synchronize(self):
         _check("xrs_synchronize", self.lib.xrs_synchronize(self.h))
 

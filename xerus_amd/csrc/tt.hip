@@ -307,11 +307,13 @@ struct HostMarks {
         std::snprintf(buf, sizeof(buf), " %s %.0f", what, us);
         line += buf;
     }
+    HostMarks();
     ~HostMarks();
 };
-HostMarks* g_marks = nullptr;
+thread_local HostMarks* g_marks = nullptr;   // the marks of the round this thread is in (stamps on), else null
+HostMarks::HostMarks() { g_marks = on ? this : nullptr; }
 HostMarks::~HostMarks() {
-    if (g_marks == this) g_marks = nullptr;
+    g_marks = nullptr;
     if (on) std::fprintf(stderr, "[round host us]%s\n", line.c_str());
 }
 #define XRS_MARK(what) do { if (g_marks) g_marks->mark(what); } while (0)
@@ -369,8 +371,7 @@ void gemm_grouped(xrs_handle_t h, const std::vector<GemmJob>& jobs) {
     }
 }
 
-struct ChainPass {
-    std::vector<double*> C;   // new cores (owned by the TT's pool until replaced / released)
+struct ChainStatus {
     int* status = nullptr;    // pinned host copy of the factorisation statuses
     int count = 0;
 };
@@ -382,8 +383,9 @@ struct ChainPass {
 // C_0 = M_0 (I (x) L_1). In exact arithmetic the C_k (k >= 1) have orthonormal rows and represent the
 // same tensor. Nothing is synchronised: the factorisation statuses are copied to pinned host memory
 // behind the transforms and judged by chain_check (a failed factorisation only makes C garbage, which
-// is then discarded).
-void chain_pass(TT& t, bool certify, ChainPass& out) {
+// is then discarded). The new cores C are candidates owned by `sw`; the pass's own temporaries go back to
+// the pool when it returns (stream-ordered: the check's buffers reuse them).
+ChainStatus chain_pass(Sweep& sw, TT& t, bool certify, std::vector<double*>& C) {
     const size_t d = t.d;
     xrs_handle_t h = t.h;
     std::vector<double*> G, H;
@@ -412,16 +414,14 @@ void chain_pass(TT& t, bool certify, ChainPass& out) {
     chol_enqueue(h, jobs, st.as<int>(), Cs);
     XRS_HIP(hipMemcpyAsync(host_status, st.d(), size_t(cnt) * 4, hipMemcpyDeviceToHost, h->stream));
     XRS_MARK("potrf");
-    out.status = host_status;
-    out.count = cnt;
     // The d transforms are independent: same-shape GEMMs go out as one batched launch each, all on the
     // main stream (cross-stream event hops cost ~20 us each here; a batch fills the chip as well as
     // concurrent streams do). The left factor is applied as a GEMM with the explicit inverse
     // Z_k = L_k^{-1} (one batched launch); the check below certifies the result either way.
-    out.C.assign(d, nullptr);
+    C.assign(d, nullptr);
     std::vector<DevBuf> W(d);
     for (size_t k = 0; k < d; ++k) {
-        out.C[k] = t.alloc(t.size(k));
+        C[k] = sw.core(t.size(k));
         if (k > 0 && k + 1 < d) W[k] = DevBuf(h, t.size(k) * 8);
     }
     // L_k and Z_k of the register-resident kernels (r <= 256) hold exact zeros above the diagonal: their
@@ -429,68 +429,68 @@ void chain_pass(TT& t, bool certify, ChainPass& out) {
     std::vector<GemmJob> right, left;
     for (size_t k = 0; k + 1 < d; ++k) {   // right factors: M_k (I (x) L_{k+1}), (r_k n_k) x r_{k+1} x r_{k+1}
         const size_t b = t.r[k + 1];
-        right.push_back({t.rows_left(k), b, b, b, b, false, false, t.core[k], Lf[k + 1].d(), k == 0 ? out.C[k] : W[k].d()});
+        right.push_back({t.rows_left(k), b, b, b, b, false, false, t.core[k], Lf[k + 1].d(), k == 0 ? C[k] : W[k].d()});
         right.back().tri = b <= 256 ? kTriB : 0;
     }
     for (size_t k = 1; k < d; ++k) {       // left factors: Z_k (r_k x r_k) times the r_k x (n_k r_{k+1}) unfolding
         const size_t a = t.r[k], cols = t.cols_right(k);
-        left.push_back({a, cols, a, a, cols, false, false, Z[k].d(), k + 1 < d ? W[k].d() : t.core[k], out.C[k]});
+        left.push_back({a, cols, a, a, cols, false, false, Z[k].d(), k + 1 < d ? W[k].d() : t.core[k], C[k]});
         left.back().tri = a <= 256 ? kTriA : 0;
     }
     gemm_grouped(h, right);
     gemm_grouped(h, left);
     XRS_MARK("transforms");
+    return {host_status, cnt};
 }
 
 // True when every factorisation of the pass succeeded (valid after the stream has been synchronised).
-bool chain_status_ok(const ChainPass& p) {
+bool chain_status_ok(const ChainStatus& p) {
     static const bool dbg = std::getenv("XRS_DEBUG_ROUND") != nullptr;
-    for (int i = 0; i < p.count; ++i)
-        if (p.status[i] != 0) {
-            if (dbg) std::fprintf(stderr, "chain_pass: status word %d of %d is %d (a factorisation failed)\n", i, p.count, p.status[i]);
-            return false;
-        }
-    return true;
+    const int i = first_bad(p.status, p.count);
+    if (i >= 0 && dbg) std::fprintf(stderr, "chain_pass: status word %d of %d is %d (a factorisation failed)\n", i, p.count, p.status[i]);
+    return i < 0;
+}
+
+int orth_enqueue(TT& t, std::vector<DevBuf>& keep, const std::vector<double*>& C, const size_t* r, bool rows, double* host) {
+    xrs_handle_t h = t.h;
+    const size_t first = rows ? 1 : 0, cnt = t.d - 1;
+    size_t total = 0;
+    for (size_t i = 0; i < cnt; ++i) total += r[i + 1] * r[i + 1];   // (both kinds: the Gram of edge i + 1)
+    keep.emplace_back(h, (total + cnt * kOrthSlices) * 8);
+    double* all = keep.back().d();   // contiguous: one all-reduce for every Gram when sharded
+    std::vector<GemmJob> grams;
+    DevIdArgs da{};
+    size_t off = 0;
+    for (size_t i = 0; i < cnt; ++i) {
+        const size_t k = first + i, g = r[i + 1], len = rows ? t.n[k] * r[k + 1] : r[k] * t.n[k];
+        const double* X = C[k];
+        double* G = all + off;
+        off += g * g;
+        if (rows) grams.push_back({g, g, len, len, len, false, true, X, X, G, true});
+        else grams.push_back({g, g, len, g, g, true, false, X, X, G, true});
+        da.G[i] = G;
+        da.n[i] = int(g);
+    }
+    gemm_grouped(h, grams);
+    t.reduce(all, total);   // sharded: complete the mode sums across ranks (no-op otherwise)
+    da.out = all + total;
+    hipLaunchKernelGGL(k_dev_identity_many, dim3(unsigned(cnt), kOrthSlices), dim3(256), 0, h->stream, da);
+    check_launch("k_dev_identity_many");
+    XRS_HIP(hipMemcpyAsync(host, da.out, cnt * kOrthSlices * 8, hipMemcpyDeviceToHost, h->stream));
+    return int(cnt) * kOrthSlices;
 }
 
 // max_k max |C_k C_k^T - I| over cores 1..d-1 (mode sums completed across ranks when sharded).
 // Synchronises the stream (so the pass statuses are readable afterwards).
 double chain_check(TT& t, const std::vector<double*>& C) {
-    const size_t d = t.d;
-    xrs_handle_t h = t.h;
     XRS_MARK("check");
-    std::vector<double*> Gr(d, nullptr);
-    DevIdArgs da{};
-    DevBuf dev(h, d * 16 * 8 + 64);
-    int nchk = 0;
-    size_t gtot = 0;
-    for (size_t k = 1; k < d; ++k) gtot += t.r[k] * t.r[k];
-    DevBuf Gall(h, gtot * 8);   // contiguous: one all-reduce for every Gram when sharded
-    for (size_t k = 1, off = 0; k < d; off += t.r[k] * t.r[k], ++k) Gr[k] = Gall.d() + off;
-    std::vector<GemmJob> grams;
-    for (size_t k = 1; k < d; ++k) {
-        const size_t a = t.r[k], cols = t.cols_right(k);
-        grams.push_back({a, a, cols, cols, cols, false, true, C[k], C[k], Gr[k], true});
-    }
-    gemm_grouped(h, grams);
-    t.reduce(Gall.d(), gtot);   // sharded: complete the mode sums across ranks (no-op otherwise)
-    for (size_t k = 1; k < d; ++k) {
-        da.G[nchk] = Gr[k];
-        da.n[nchk] = int(t.r[k]);
-        ++nchk;
-    }
-    da.out = dev.d();
-    constexpr int kSlices = 16;
-    hipLaunchKernelGGL(k_dev_identity_many, dim3(nchk, kSlices), dim3(256), 0, h->stream, da);
-    check_launch("k_dev_identity_many");
-    double* hd = scratch::host<double>(h, scratch::kHostChainDev, size_t(nchk) * kSlices);
-    XRS_HIP(hipMemcpyAsync(hd, dev.d(), size_t(nchk) * kSlices * 8, hipMemcpyDeviceToHost, h->stream));
+    std::vector<DevBuf> keep;
+    double* hd = scratch::host<double>(t.h, scratch::kHostChainDev, (t.d - 1) * kOrthSlices);
+    const int nchk = orth_enqueue(t, keep, C, t.r, true, hd);
     XRS_MARK("enq");
-    host_wait(h);
+    host_wait(t.h);
     XRS_MARK("sync");
-    double worst = 0.0;
-    for (int i = 0; i < nchk * kSlices; ++i) worst = (hd[i] > worst || hd[i] != hd[i]) ? hd[i] : worst;
-    return worst;
+    return worst_dev(hd, nchk);
 }
 
 // Chain form of the certified round (no factorisation on a sequential chain): pass 1 certifies both
@@ -508,40 +508,31 @@ bool round_chain(TT& t, const size_t* max_ranks, double eps) {
     const double cX = 0.5 * std::sqrt(kGramShift);
     if (!(eps < 0.25 * cX * cX)) return false;
     HostMarks marks;
-    g_marks = marks.on ? &marks : nullptr;
-    ChainPass p1;
-    chain_pass(t, true, p1);
-    double dev = chain_check(t, p1.C);
-    if (!chain_status_ok(p1)) {
-        for (size_t k = 0; k < d; ++k) t.release(p1.C[k]);
-        { g_marks = nullptr; return false; }
-    }
-    std::vector<double*> C = p1.C;
+    Sweep sw(t);
+    std::vector<double*> C;
+    const ChainStatus p1 = chain_pass(sw, t, true, C);
+    double dev = chain_check(t, C);
+    if (!chain_status_ok(p1)) return false;
     if (!(dev <= kOrthTol)) {
         if (dbg) std::fprintf(stderr, "round_chain: pass 1 orthogonality %.3e, second pass\n", dev);
         TT t2 = t;
         t2.core = C.data();
-        ChainPass p2;
-        chain_pass(t2, false, p2);
-        const double dev2 = chain_check(t2, p2.C);
+        std::vector<double*> C2;
+        const ChainStatus p2 = chain_pass(sw, t2, false, C2);
+        const double dev2 = chain_check(t2, C2);
         const bool ok2 = chain_status_ok(p2);
         if (dbg) std::fprintf(stderr, "round_chain: pass 2 orthogonality %.3e (factors %s)\n", dev2, ok2 ? "ok" : "failed");
-        if (ok2 && dev2 <= kOrthTol) {
-            for (size_t k = 0; k < d; ++k) t.release(C[k]);
-            C = p2.C;
+        const bool take2 = ok2 && dev2 <= kOrthTol;
+        for (double* p : take2 ? C : C2) sw.drop(p);
+        if (take2) {
+            C = C2;
             dev = dev2;
-        } else {
-            for (size_t k = 0; k < d; ++k) t.release(p2.C[k]);
         }
     }
     const bool ok = dev <= kOrthTol;
-    if (!ok && t.sharded()) {   // no sharded sequential sweep: report, cores untouched
-        for (size_t k = 0; k < d; ++k) t.release(C[k]);
-        { g_marks = nullptr; return false; }
-    }
-    for (size_t k = 0; k < d; ++k) t.replace(k, C[k]);
+    if (!ok && t.sharded()) return false;   // no sharded sequential sweep: report, cores untouched
+    sw.commit(C);
     if (!ok) rl_sweep(t, max_ranks, eps, cX, d - 1);
-    g_marks = nullptr;
     return true;
 }
 
@@ -549,15 +540,13 @@ bool round_chain(TT& t, const size_t* max_ranks, double eps) {
 // right-orthonormal -- the truncating round's output when its Gram-based cores missed the tolerance:
 // same tensor and ranks, orthonormality restored to ~u. False (cores untouched) if the pass failed.
 bool reorthonormalize(TT& t) {
-    ChainPass p;
-    chain_pass(t, false, p);
-    const double dev = chain_check(t, p.C);
-    const bool ok = chain_status_ok(p) && dev <= kOrthTol;
-    for (size_t k = 0; k < t.d; ++k) {
-        if (ok) t.replace(k, p.C[k]);
-        else t.release(p.C[k]);
-    }
-    return ok;
+    Sweep sw(t);
+    std::vector<double*> C;
+    const ChainStatus p = chain_pass(sw, t, false, C);
+    const double dev = chain_check(t, C);
+    if (!(chain_status_ok(p) && dev <= kOrthTol)) return false;
+    sw.commit(C);
+    return true;
 }
 
 // Sequential certified right-to-left CholeskyQR sweep from edge `from` down to 1 (the unfoldings are

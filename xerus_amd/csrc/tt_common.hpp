@@ -1,6 +1,11 @@
 // Internal interface of the TT drivers (tt.hip: move_core, certified chain round, <x,y>; tt_trunc.hip:
-// the certified truncating round). Not part of the C-ABI.
+// the certified truncating round). Not part of the C-ABI. Shared by the three device-resident rounds:
+//   Sweep                 owner of a round's temporaries and candidate cores (released unless committed)
+//   orth_enqueue          the orthogonality check of a core vector, enqueued up to its pinned copy
+//   worst_dev, first_bad  the host-side judges of that copy and of the factorisation statuses
+//   gram_chains, gemm_grouped, k_dev_identity_many
 #pragma once
+#include <algorithm>
 #include <vector>
 
 #include "chol_batch.hpp"
@@ -61,6 +66,49 @@ struct TT {
     }
 };
 
+// Everything a device-resident round has enqueued and not yet judged. `keep`: temporaries that must outlive
+// the enqueued work. `owned`: the candidate cores, pool blocks that become the TT's cores through commit();
+// whatever is still owned when the round leaves, by a return or a throw, goes back to the pool.
+struct Sweep {
+    TT& t;
+    std::vector<DevBuf> keep;
+    std::vector<double*> owned;
+    explicit Sweep(TT& tt) : t(tt) {}
+    Sweep(const Sweep&) = delete;
+    Sweep& operator=(const Sweep&) = delete;
+    ~Sweep() {
+        for (double* p : owned) {
+            try {
+                t.release(p);
+            } catch (...) {   // (fence_readers: the block stays out of the pool rather than under a reader)
+            }
+        }
+    }
+    double* buf(size_t elems) {
+        keep.emplace_back(t.h, std::max<size_t>(elems, 1) * 8);
+        return keep.back().d();
+    }
+    double* core(size_t elems) {
+        double* p = t.alloc(elems);
+        owned.push_back(p);
+        return p;
+    }
+    void drop(double* p) {   // a core block that is no longer needed
+        auto it = std::find(owned.begin(), owned.end(), p);
+        if (it != owned.end()) {
+            owned.erase(it);
+            t.release(p);
+        }
+    }
+    // the candidates C (all owned) become the TT's cores, with the internal ranks r[1..d-1] when given
+    void commit(const std::vector<double*>& C, const size_t* r = nullptr) {
+        fence_readers(t.h);   // the one step of replace() that can throw, before any ownership moves
+        for (size_t k = 0; k < t.d; ++k) t.replace(k, C[k]);
+        owned.clear();
+        for (size_t k = 1; r && k < t.d; ++k) t.r[k] = r[k];
+    }
+};
+
 // Mode layout of a sharded TT (tt_trunc.hip): global mode sizes ng, this rank's first slice off per mode;
 // known = false when the ranks' order is unknown (world 0) -- then off is meaningless.
 struct ShardLayout {
@@ -105,6 +153,25 @@ struct DevIdArgs {
 };
 // max |G_i - I| of a batch of square matrices; out[i * gridDim.y + slice]
 __global__ void k_dev_identity_many(const DevIdArgs args);
+
+// The orthogonality check of the cores C with ranks r (d + 1): max |C_k C_k^T - I| of the right unfoldings of
+// cores 1..d-1 (`rows`) or max |C_k^T C_k - I| of the left unfoldings of cores 0..d-2, kOrthSlices values per
+// core. Enqueues the Grams (one buffer, pushed onto `keep`; sharded: completed by ONE all-reduce), the
+// deviations and their copy to the pinned `host`; returns the number of values, valid after the next host wait.
+constexpr int kOrthSlices = 16;
+int orth_enqueue(TT& t, std::vector<DevBuf>& keep, const std::vector<double*>& C, const size_t* r, bool rows, double* host);
+// NaN-propagating maximum of the check's values
+inline double worst_dev(const double* v, int count) {
+    double worst = 0.0;
+    for (int i = 0; i < count; ++i) worst = (v[i] > worst || v[i] != v[i]) ? v[i] : worst;
+    return worst;
+}
+// first non-zero status word, -1 when every factorisation succeeded
+inline int first_bad(const int* status, int count) {
+    for (int i = 0; i < count; ++i)
+        if (status[i] != 0) return i;
+    return -1;
+}
 
 // Independent GEMMs; the ones of identical shape go out as one batched launch.
 struct GemmJob {

@@ -36,62 +36,6 @@ namespace {
 constexpr double kTruncOrthTol = 1e-12;    // max |C C^T - I| of a canonical core; above it: one chain pass
 constexpr double kTruncAcceptTol = 1e-8;   // above it the sweep is rejected (reference algorithm instead)
 
-// Host-side record of everything enqueued; buffers are released once the sweep is judged.
-struct Sweep {
-    TT& t;
-    std::vector<DevBuf> keep;
-    std::vector<double*> owned;   // pool blocks that become cores on success (released on failure)
-    explicit Sweep(TT& tt) : t(tt) {}
-    double* buf(size_t elems) {
-        keep.emplace_back(t.h, std::max<size_t>(elems, 1) * 8);
-        return keep.back().d();
-    }
-    double* core(size_t elems) {
-        double* p = t.alloc(elems);
-        owned.push_back(p);
-        return p;
-    }
-    void drop(double* p) {   // a core block that is no longer needed
-        auto it = std::find(owned.begin(), owned.end(), p);
-        if (it != owned.end()) {
-            owned.erase(it);
-            t.release(p);
-        }
-    }
-    void discard() {
-        for (double* p : owned) t.release(p);
-        owned.clear();
-    }
-};
-
-// max |X X^T - I| (rows, `rows` = true) or max |X^T X - I| of a list of matrices -> dev[0..count*16);
-// the Grams sit in one buffer, completed across ranks by ONE all-reduce when sharded
-void orth_devs(Sweep& sw, const std::vector<const double*>& X, const std::vector<size_t>& m, const std::vector<size_t>& n,
-               bool rows, double* dev) {
-    xrs_handle_t h = sw.t.h;
-    const size_t cnt = X.size();
-    size_t total = 0;
-    for (size_t i = 0; i < cnt; ++i) total += (rows ? m[i] : n[i]) * (rows ? m[i] : n[i]);
-    double* all = sw.buf(total);
-    std::vector<GemmJob> grams;
-    DevIdArgs da{};
-    size_t off = 0;
-    for (size_t i = 0; i < cnt; ++i) {
-        const size_t g = rows ? m[i] : n[i];
-        double* G = all + off;
-        off += g * g;
-        if (rows) grams.push_back({g, g, n[i], n[i], n[i], false, true, X[i], X[i], G, true});
-        else grams.push_back({g, g, m[i], g, g, true, false, X[i], X[i], G, true});
-        da.G[i] = G;
-        da.n[i] = int(g);
-    }
-    gemm_grouped(h, grams);
-    sw.t.reduce(all, total);
-    da.out = dev;
-    hipLaunchKernelGGL(k_dev_identity_many, dim3(unsigned(cnt), 16), dim3(256), 0, h->stream, da);
-    check_launch("k_dev_identity_many");
-}
-
 // wide edge, B = L Q with the left singular vectors of L as the rows of Ut (Jacobi on the columns of L):
 // M = S^{-1} Ut[:kk] (new core = M B = Vt_kk Q) and T = Ut[:kk]^T S (= U S, core_{k-1} <- core_{k-1} T)
 __global__ void __launch_bounds__(256) k_edge_factors(const double* __restrict__ Ut, const double* __restrict__ S, int r, int kk,
@@ -277,7 +221,7 @@ bool round_truncate(TT& t, const size_t* max_ranks, double eps) {
     constexpr int kStatusWords = 1024, kJacobiSlot = 768;
     // (a left pass or a sweep: at most d - 1 <= 63 edges x 2 jobs x the 4 status words of a 1024 x 1024 job)
     static_assert(63 * 2 * 4 <= kJacobiSlot && kHugeMax <= 1024);
-    DevBuf st(h, kStatusWords * 4), devb(h, 64 * 16 * 8);
+    DevBuf st(h, kStatusWords * 4);
     int* status = st.as<int>();
     int nst = 0;
     XRS_HIP(hipMemsetAsync(status, 0, kStatusWords * 4, h->stream));
@@ -285,46 +229,26 @@ bool round_truncate(TT& t, const size_t* max_ranks, double eps) {
     // 1b. left chain pass (certified), and a second one on its output when a single CholeskyQR pass over
     //     the train left the cores short of orthonormal (kappa^2 u > tol: CholeskyQR2 on the whole train)
     int* hs = scratch::host<int>(h, scratch::kHostTruncStatus, kStatusWords);
-    double* hd = scratch::host<double>(h, scratch::kHostTruncDev, (d - 1) * 16);
+    double* hd = scratch::host<double>(h, scratch::kHostTruncDev, (d - 1) * kOrthSlices);
     std::vector<double*> A;
     left_pass(sw, t, t.core, true, A, status, nst);
     double worst = 0.0;
     for (int pass = 1;; ++pass) {
-        {
-            std::vector<const double*> X;
-            std::vector<size_t> m, n;
-            for (size_t k = 0; k + 1 < d; ++k) {
-                X.push_back(A[k]);
-                m.push_back(t.rows_left(k));
-                n.push_back(t.r[k + 1]);
-            }
-            orth_devs(sw, X, m, n, false, devb.d());
-        }
         // check point (one host sync): the factorisations and the left-canonical form
-        const int nchk = int(d - 1) * 16;
+        const int nchk = orth_enqueue(t, sw.keep, A, t.r, false, hd);
         XRS_HIP(hipMemcpyAsync(hs, status, size_t(nst) * 4, hipMemcpyDeviceToHost, h->stream));
-        XRS_HIP(hipMemcpyAsync(hd, devb.d(), size_t(nchk) * 8, hipMemcpyDeviceToHost, h->stream));
         host_wait(h);
         if (core_range_exceeded(t)) {   // (round(): repeated on range-controlled cores)
             t.range_hit = true;
-            sw.discard();
             return false;
         }
-        bool ok = true;
-        for (int i = 0; i < nst; ++i) ok = ok && hs[i] == 0;
-        worst = 0.0;
-        for (int i = 0; i < nchk; ++i) worst = (hd[i] > worst || hd[i] != hd[i]) ? hd[i] : worst;
+        const bool ok = first_bad(hs, nst) < 0;
+        worst = worst_dev(hd, nchk);
         if (dbg) std::fprintf(stderr, "round_truncate: left pass %d %s, orthogonality %.3e\n", pass,
                               ok ? "certified" : "NOT certified", worst);
-        if (!ok) {
-            sw.discard();
-            return false;
-        }
+        if (!ok) return false;
         if (worst <= kTruncOrthTol) break;
-        if (pass == 2) {
-            sw.discard();
-            return false;
-        }
+        if (pass == 2) return false;
         std::vector<double*> A1 = A;
         nst = 0;
         XRS_HIP(hipMemsetAsync(status, 0, kStatusWords * 4, h->stream));
@@ -340,7 +264,22 @@ bool round_truncate(TT& t, const size_t* max_ranks, double eps) {
     // certificates of the eigensolver edges on side stream 0 (off the sweep's critical path), when this
     // handle owns its streams and is not inside a fork
     const bool cert_side = !h->borrowed_streams && h->stream == h->own_stream && h->side_stream[0] && h->prof_mask == 0;
-    bool side_used = false;
+    // once certificates are forked, every exit (a throw too) orders the main stream behind the side stream
+    // before `st` and the sweep's buffers go back to the pool
+    struct SideJoin {
+        xrs_handle_t h;
+        bool used = false;
+        void join() {
+            if (!used) return;
+            XRS_HIP(hipEventRecord(h->ev_join[0], h->side_stream[0]));
+            XRS_HIP(hipStreamWaitEvent(h->stream, h->ev_join[0], 0));
+            used = false;
+        }
+        ~SideJoin() {
+            if (used && hipEventRecord(h->ev_join[0], h->side_stream[0]) == hipSuccess)
+                (void)hipStreamWaitEvent(h->stream, h->ev_join[0], 0);
+        }
+    } side{h};
     auto enqueue_chol = [&](const std::vector<CholJob>& jobs) {
         const int c = chol_status_count(jobs);
         XRS_REQUIRE(nst + c <= kJacobiSlot, "round_truncate: too many factorisation statuses");
@@ -352,7 +291,7 @@ bool round_truncate(TT& t, const size_t* max_ranks, double eps) {
         if (pending_cert.empty()) return;
         XRS_HIP(hipEventRecord(h->ev_fork, h->stream));
         XRS_HIP(hipStreamWaitEvent(h->side_stream[0], h->ev_fork, 0));
-        side_used = true;
+        side.used = true;
         StreamSwap on_side(h, h->side_stream[0]);   // (restores h->stream on scope exit, also on a throw)
         enqueue_chol(pending_cert);
         pending_cert.clear();
@@ -366,11 +305,6 @@ bool round_truncate(TT& t, const size_t* max_ranks, double eps) {
         const bool tall_gather = !wide && t.sharded();
         if (tall_gather && !lay.known) {
             if (dbg) std::fprintf(stderr, "round_truncate: sharded tall edge %zu, rank layout unknown -> not certified\n", k);
-            if (side_used) {   // the side stream may still read this sweep's buffers
-                XRS_HIP(hipEventRecord(h->ev_join[0], h->side_stream[0]));
-                XRS_HIP(hipStreamWaitEvent(h->stream, h->ev_join[0], 0));
-            }
-            sw.discard();
             return false;
         }
         const size_t Nw = tall_gather ? Ng : N;   // columns of the edge matrix as factorised here
@@ -438,44 +372,23 @@ bool round_truncate(TT& t, const size_t* max_ranks, double eps) {
         rr[k] = kk;
     }
     flush_certs();
-    if (side_used) {   // join: the side stream's certificates before the statuses are read
-        XRS_HIP(hipEventRecord(h->ev_join[0], h->side_stream[0]));
-        XRS_HIP(hipStreamWaitEvent(h->stream, h->ev_join[0], 0));
-    }
-    // right-orthonormality of the new cores 1..d-1
-    {
-        std::vector<const double*> X;
-        std::vector<size_t> m, n;
-        for (size_t k = 1; k < d; ++k) {
-            X.push_back(A[k]);
-            m.push_back(rr[k]);
-            n.push_back(t.n[k] * rr[k + 1]);   // (local columns; the Grams are all-reduced)
-        }
-        orth_devs(sw, X, m, n, true, devb.d());
-    }
-    const int nchk2 = int(d - 1) * 16;
+    side.join();   // the side stream's certificates before the statuses are read
+    // right-orthonormality of the new cores 1..d-1 (local columns; the Grams are all-reduced)
+    const int nchk2 = orth_enqueue(t, sw.keep, A, rr.data(), true, hd);
     XRS_HIP(hipMemcpyAsync(hs, status, size_t(kStatusWords) * 4, hipMemcpyDeviceToHost, h->stream));
-    XRS_HIP(hipMemcpyAsync(hd, devb.d(), size_t(nchk2) * 8, hipMemcpyDeviceToHost, h->stream));
     host_wait(h);
-    bool ok = true;
-    for (int i = 0; i < nst; ++i) ok = ok && hs[i] == 0;
+    bool ok = first_bad(hs, nst) < 0;
     int max_sweeps = 0;
     for (size_t i = 0; i < jst.size(); ++i) {
         const int s = hs[kJacobiSlot + int(i)];
         ok = ok && s >= 0;
         max_sweeps = std::max(max_sweeps, s);
     }
-    worst = 0.0;
-    for (int i = 0; i < nchk2; ++i) worst = (hd[i] > worst || hd[i] != hd[i]) ? hd[i] : worst;
+    worst = worst_dev(hd, nchk2);
     if (dbg) std::fprintf(stderr, "round_truncate: sweep %s, max Jacobi sweeps %d, orthogonality %.3e\n",
                           ok ? "certified" : "NOT certified", max_sweeps, worst);
-    if (!ok || !(worst <= kTruncAcceptTol)) {
-        sw.discard();
-        return false;
-    }
-    for (size_t k = 0; k < d; ++k) t.replace(k, A[k]);
-    sw.owned.clear();
-    for (size_t k = 1; k < d; ++k) t.r[k] = rr[k];
+    if (!ok || !(worst <= kTruncAcceptTol)) return false;
+    sw.commit(A, rr.data());
     // the new cores S^-1 U^T B carry kappa(B_kk)^2 u of non-orthogonality: one chain pass if that is
     // above the canonical-form tolerance (the represented tensor and the ranks are final already)
     if (worst > kTruncOrthTol) {
@@ -678,7 +591,7 @@ bool round_general(TT& t, const size_t* max_ranks, double eps) {
 
     Sweep sw(t);
     constexpr int kSlots = 2048;
-    DevBuf stb(h, kSlots * 4), devb(h, 64 * 16 * 8);
+    DevBuf stb(h, kSlots * 4);
     int* st = stb.as<int>();
     XRS_HIP(hipMemsetAsync(st, 0, kSlots * 4, h->stream));
     int nst = 0;
@@ -687,6 +600,7 @@ bool round_general(TT& t, const size_t* max_ranks, double eps) {
     std::vector<double*> A(t.core, t.core + d);   // current cores (originals untouched)
     std::vector<size_t> rr(t.r, t.r + d + 1);
     int* hs = scratch::host<int>(h, scratch::kHostGeneralStatus, kSlots);
+    double* hd = scratch::host<double>(h, scratch::kHostTruncDev, (d - 1) * kOrthSlices);
 
     // 1a. left to right as shifted CholeskyQR3 over the whole train: three chain passes (Gram chain
     //     G_{k+1} = M_k^T (G_k (x) I) M_k, ONE batched Cholesky launch of G_k + s tr(G_k) I (first pass) /
@@ -726,40 +640,19 @@ bool round_general(TT& t, const size_t* max_ranks, double eps) {
             check_launch("k_rank_cert_gram");
             ++cst;
         }
-        {
-            std::vector<const double*> X;
-            std::vector<size_t> m, n;
-            for (size_t k = 0; k + 1 < d; ++k) {
-                X.push_back(A3[k]);
-                m.push_back(rr[k] * t.n[k]);
-                n.push_back(rr[k + 1]);
-            }
-            orth_devs(sw, X, m, n, false, devb.d());
-        }
-        double* hd = scratch::host<double>(h, scratch::kHostTruncDev, (d - 1) * 16);
-        const int nchk = int(d - 1) * 16;
+        const int nchk = orth_enqueue(t, sw.keep, A3, rr.data(), false, hd);
         XRS_HIP(hipMemcpyAsync(hs, st, size_t(cst) * 4, hipMemcpyDeviceToHost, h->stream));
-        XRS_HIP(hipMemcpyAsync(hd, devb.d(), size_t(nchk) * 8, hipMemcpyDeviceToHost, h->stream));
         host_wait(h);
         if (core_range_exceeded(t)) {   // (round(): repeated on range-controlled cores)
             t.range_hit = true;
-            sw.discard();
             return false;
         }
-        chain_ok = true;
-        int first_bad = -1;
-        for (int i = 0; i < cst; ++i)
-            if (hs[i] != 0) {
-                chain_ok = false;
-                first_bad = i;
-                break;
-            }
-        double worst = 0.0;
-        for (int i = 0; i < nchk; ++i) worst = (hd[i] > worst || hd[i] != hd[i]) ? hd[i] : worst;
-        chain_ok = chain_ok && worst <= kTruncOrthTol;
+        const int bad = first_bad(hs, cst);
+        const double worst = worst_dev(hd, nchk);
+        chain_ok = bad < 0 && worst <= kTruncOrthTol;
         if (dbg)
             std::fprintf(stderr, "round_general: chain left sweep %s (first bad slot %d of %d, rank certificates from %d), orthogonality %.3e\n",
-                         chain_ok ? "certified" : "NOT certified", first_bad, cst, crank, worst);
+                         chain_ok ? "certified" : "NOT certified", bad, cst, crank, worst);
         if (chain_ok) {
             A = A3;
         } else {
@@ -771,10 +664,7 @@ bool round_general(TT& t, const size_t* max_ranks, double eps) {
     // 1b. otherwise core by core: A_k = Q_k, next = R_k core_{k+1}, each by shifted CholeskyQR3
     for (size_t k = 0; !chain_ok && k + 1 < d; ++k) {
         const size_t m = rr[k] * t.n[k], b = rr[k + 1];
-        if (rr[k] * ng[k] < b) {   // (sharded with an unknown layout: the excess could not be removed)
-            sw.discard();
-            return false;
-        }
+        if (rr[k] * ng[k] < b) return false;   // (sharded with an unknown layout: the excess could not be removed)
         double* Q = sw.core(m * b);
         double* R = sw.buf(b * b);
         double* Rinv = sw.buf(b * b);
@@ -824,7 +714,6 @@ bool round_general(TT& t, const size_t* max_ranks, double eps) {
         const bool tall_gather = !wide && sharded;
         if (tall_gather && !lay.known) {
             if (dbg) std::fprintf(stderr, "round_general: sharded tall edge %zu, rank layout unknown -> not certified\n", k);
-            sw.discard();
             return false;
         }
         const size_t Nw = tall_gather ? Ng : N;
@@ -876,14 +765,8 @@ bool round_general(TT& t, const size_t* max_ranks, double eps) {
     // 3. the synchronisation: statuses, Jacobi sweeps, device ranks
     XRS_HIP(hipMemcpyAsync(hs, st, size_t(kSlots) * 4, hipMemcpyDeviceToHost, h->stream));
     host_wait(h);
-    bool ok = true;
-    int bad = -1;
-    for (int i = 0; i < nst; ++i)
-        if (hs[i] != 0) {
-            ok = false;
-            bad = i;
-            break;
-        }
+    const int bad = first_bad(hs, nst);
+    bool ok = bad < 0;
     int max_sweeps = 0;
     for (size_t i = 0; i < jac.size(); ++i) {
         ok = ok && hs[kJac + int(i)] >= 0;
@@ -901,10 +784,7 @@ bool round_general(TT& t, const size_t* max_ranks, double eps) {
         for (size_t i = 0; i < jac.size(); ++i) std::fprintf(stderr, " %d:%d", jac[i], hs[kJac + int(i)]);
         std::fprintf(stderr, "\n");
     }
-    if (!ok) {
-        sw.discard();
-        return false;
-    }
+    if (!ok) return false;
     // 4. compaction to the device ranks: core_k[:kk_k, :, :kk_{k+1}]
     std::vector<double*> C(d, nullptr);
     for (size_t k = 0; k < d; ++k) {
@@ -919,30 +799,12 @@ bool round_general(TT& t, const size_t* max_ranks, double eps) {
         sw.drop(A[k]);
     }
     // right-orthonormality of cores 1..d-1 (S^{-1} U^T B carries kappa(B_kk) u of deviation)
-    {
-        std::vector<const double*> X;
-        std::vector<size_t> m, n;
-        for (size_t k = 1; k < d; ++k) {
-            X.push_back(C[k]);
-            m.push_back(kk[k]);
-            n.push_back(t.n[k] * kk[k + 1]);
-        }
-        orth_devs(sw, X, m, n, true, devb.d());
-    }
-    double* hd = scratch::host<double>(h, scratch::kHostTruncDev, (d - 1) * 16);
-    const int nchk = int(d - 1) * 16;
-    XRS_HIP(hipMemcpyAsync(hd, devb.d(), size_t(nchk) * 8, hipMemcpyDeviceToHost, h->stream));
+    const int nchk = orth_enqueue(t, sw.keep, C, kk.data(), true, hd);
     host_wait(h);
-    double worst = 0.0;
-    for (int i = 0; i < nchk; ++i) worst = (hd[i] > worst || hd[i] != hd[i]) ? hd[i] : worst;
+    const double worst = worst_dev(hd, nchk);
     if (dbg) std::fprintf(stderr, "round_general: right orthogonality %.3e\n", worst);
-    if (!(worst <= kTruncAcceptTol)) {
-        sw.discard();
-        return false;
-    }
-    for (size_t k = 0; k < d; ++k) t.replace(k, C[k]);
-    sw.owned.clear();
-    for (size_t k = 1; k < d; ++k) t.r[k] = kk[k];
+    if (!(worst <= kTruncAcceptTol)) return false;
+    sw.commit(C, kk.data());
     if (worst > kTruncOrthTol) {
         const bool re = reorthonormalize(t);
         if (dbg) std::fprintf(stderr, "round_general: re-orthonormalised (%s)\n", re ? "ok" : "failed");
