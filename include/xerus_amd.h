@@ -102,6 +102,21 @@ int xrs_gemm_sym(xrs_handle_t handle, double* C, size_t N, double alpha,
                  const double* A, size_t lda, int transA, size_t K,
                  const double* B, size_t ldb, int transB);
 
+/** The internal operand forms of the GEMM family behind one entry point, exposed for their tests: `count`
+ *  same-shape products C[i] = alpha * op(A[i]) * op(B[i]) (A, B, C: host arrays of device pointers, argument
+ *  checks as xrs_gemm_batched), dispatched as the TT rounds dispatch a group: count == 1 with sym to the
+ *  xrs_gemm_sym kernel path, count == 1 to the single GEMM with `tri`, else to the batch with `sym` and `tri`.
+ *  sym != 0: the products are known symmetric (M == N, else XRS_EINVAL); only the lower tiles are computed
+ *  and every C[i] is written exactly symmetric.
+ *  tri: 0, 1 (op(A) lower triangular: op(A)[m][k] = 0 for k > m) or 2 (op(B) lower triangular: op(B)[k][n] = 0
+ *  for k < n); any other value is XRS_EINVAL. The caller guarantees EXACT zeros outside the triangle. tri is
+ *  a permission to skip the K-blocks that lie wholly in the zero part, not a mask: a kernel may still read
+ *  any element, the result equals that of tri = 0 bit for bit, and nonzero values outside the triangle give
+ *  an unspecified mix of the two products. sym and tri do not combine (XRS_EINVAL). */
+int xrs_gemm_forms(xrs_handle_t handle, size_t count, double* const* C, size_t M, size_t N, double alpha,
+                   const double* const* A, size_t lda, int transA, size_t K,
+                   const double* const* B, size_t ldb, int transB, int sym, int tri);
+
 /** fp32 form of xrs_gemm on the fp32 matrix cores (v_mfma_f32_16x16x4_f32, 157.3 TF/s peak): C = alpha *
  *  op(A) * op(B), float operands and result, row-major, ldc = N; argument order, ld rules and aliasing as
  *  xrs_gemm. The reduced-precision variant of blasWrapper::matrix_matrix_product (blasLapackWrapper.cpp:

@@ -6,6 +6,11 @@ Tolerance: relative Frobenius error <= 1e-6 (the north star's bound; the fp32 pr
 selection: 128x128 for large grids, 64x80 / 80x64 for the TT zipper's wide / tall shapes, 64x64 with split-K
 for r x r Grams, 32x32 for small outputs), with all four transposition pairs, the scalar staging path
 (ragged extents, unaligned pointers) and the in-launch split-K combine.
+
+Padded leading dimensions (test_gemm_f32_padded_ld): every staging mode with lda / ldb above the row length, the
+operands inside NaN-filled buffers and C between sentinel bands, under an elementwise dot-product bound.
+Measured on the MI355X: max(err / bound) = 0.072 over its 15 cases (worst (100, 68, 36), ld = row length + 1, NN),
+so the derived factor c = 1 stands.
 """
 import numpy as np
 import pytest
@@ -62,6 +67,85 @@ def test_gemm_f32_unaligned_and_alpha(handle, ref):
     err, same = _run(handle, ref, 256, 320, 96, False, False, alpha=2.5, offset=1)
     assert err <= 1e-6, err
     assert same
+
+
+# ---- padded leading dimensions: every staging mode inside NaN-filled buffers, an elementwise bound
+PAD_SENTINEL = np.float32(-777.25)
+PAD_GUARD = 64
+# factor on the derived bound (see test_gemm_f32_padded_ld)
+PAD_C = 1.0
+
+
+class _View:
+    """An operand inside a larger Float32Array (the C-ABI takes the pointer)."""
+
+    def __init__(self, base, off):
+        self.base = base
+        self.ptr = base.ptr + 4 * off
+
+
+def _embed_f32(handle, mat, ld, off):
+    """`mat` at float offset `off` with leading dimension `ld` inside a NaN-filled device buffer of
+    off + rows ld + 64 floats."""
+    rows, rowlen = mat.shape
+    host = np.full(off + rows * ld + 64, np.nan, dtype=np.float32)
+    host[off:off + rows * ld].reshape(rows, ld)[:, :rowlen] = mat
+    base = capi.Float32Array.from_host(handle, host)
+    assert base.ptr % 16 == 0
+    return _View(base, off)
+
+
+PADDED = [
+    # M, N, K, ld padding, staging mode reached
+    (64, 64, 64, (4, 8), 2),      # whole tiles: 16-B vectors, no masks
+    (100, 68, 36, (4, 4), 1),     # vectors with edge tiles and a ragged K-step
+    (64, 64, 64, (1, 1), 0),      # ld % 4 != 0: scalar staging
+    (100, 68, 36, (1, 1), 0),
+    (32, 32, 512, (4, 4), 2),     # split-K (4 slices, in-launch combine)
+]
+
+
+@pytest.mark.parametrize("ta,tb", [(False, False), (True, False), (False, True)])
+@pytest.mark.parametrize("M,N,K,pad,mode", PADDED)
+def test_gemm_f32_padded_ld(handle, M, N, K, pad, mode, ta, tb):
+    """lda / ldb larger than the row length in each staging mode of sgemm (vec_ok depends on ld % 4), operands
+    inside NaN-filled buffers at a 16-B aligned start, C between two 64-float sentinel bands.
+
+    Elementwise, against the fp64 product of the fp32 inputs:
+        |got - want| <= c (K + 3) 2^-24 |alpha| (|op(A)| |op(B)|).
+    c = 1 is the derived bound: v_mfma_f32_16x16x4_f32 accumulates as an fp32 fused-multiply-add chain (one
+    rounding per product), so any split of K into chains, slices and wave groups costs at most K roundings;
+    one more for alpha, two for the reference. Prints max(err / bound); the second call gives the same bits."""
+    alpha = -1.75
+    rng = np.random.default_rng(9000 + M + N + K + 2 * ta + tb + pad[0])
+    A = rng.standard_normal((K, M) if ta else (M, K)).astype(np.float32)
+    B = rng.standard_normal((N, K) if tb else (K, N)).astype(np.float32)
+    lda, ldb = A.shape[1] + pad[0], B.shape[1] + pad[1]
+    dA, dB = _embed_f32(handle, A, lda, 4), _embed_f32(handle, B, ldb, 4)
+    cbase = capi.Float32Array.from_host(handle, np.full(2 * PAD_GUARD + M * N, PAD_SENTINEL, dtype=np.float32))
+    dC = _View(cbase, PAD_GUARD)
+
+    def result():
+        host = cbase.numpy()
+        guard = np.full(PAD_GUARD, PAD_SENTINEL, dtype=np.float32)
+        assert np.array_equal(host[:PAD_GUARD], guard) and np.array_equal(host[PAD_GUARD + M * N:], guard)
+        return host[PAD_GUARD:PAD_GUARD + M * N].reshape(M, N).copy()
+
+    handle.gemm_f32(dC, M, N, alpha, dA, lda, ta, K, dB, ldb, tb)
+    got = result()
+    handle.gemm_f32(dC, M, N, alpha, dA, lda, ta, K, dB, ldb, tb)
+    assert np.array_equal(result(), got)   # deterministic
+    assert np.all(np.isfinite(got))
+    opA = (A.T if ta else A).astype(np.float64)
+    opB = (B.T if tb else B).astype(np.float64)
+    want = alpha * (opA @ opB)
+    bound = PAD_C * (K + 3) * 2.0 ** -24 * abs(alpha) * (np.abs(opA) @ np.abs(opB))
+    err = np.abs(got.astype(np.float64) - want)
+    ratio = float(np.max(err / bound))
+    print("f32 (%d, %d, %d) pad %s mode %d ta=%d tb=%d: max(err / bound) = %.3g" % (M, N, K, pad, mode, ta, tb, ratio))
+    assert np.all(err <= bound), ratio
+    for d in (dA.base, dB.base, cbase):
+        d.free()
 
 
 def test_gemm_f32_k0_and_errors(handle):

@@ -45,6 +45,8 @@ SIGNATURES = {
     "xrs_gemm_sym": (C.c_int,[_DP, _DP, _SZ, C.c_double, _DP, _SZ, C.c_int, _SZ, _DP, _SZ, C.c_int]),
     "xrs_gemm_batched": (C.c_int, [_DP, _SZ, C.POINTER(_DP), _SZ, _SZ, C.c_double, C.POINTER(_DP), _SZ, C.c_int, _SZ,
                                    C.POINTER(_DP), _SZ, C.c_int]),
+    "xrs_gemm_forms": (C.c_int, [_DP, _SZ, C.POINTER(_DP), _SZ, _SZ, C.c_double, C.POINTER(_DP), _SZ, C.c_int, _SZ,
+                                 C.POINTER(_DP), _SZ, C.c_int, C.c_int, C.c_int]),
     "xrs_permute": (C.c_int, [_DP, _DP, _DP, _SZ, C.POINTER(_SZ), C.POINTER(_SZ)]),
     "xrs_qc": (C.c_int, [_DP, _DP, _DP, C.POINTER(_SZ), _DP, _SZ, _SZ]),
     "xrs_cq": (C.c_int, [_DP, _DP, _DP, C.POINTER(_SZ), _DP, _SZ, _SZ]),
@@ -235,6 +237,14 @@ class Handle:
         tab = lambda xs: (_DP * max(1, cnt))(*[_DP(x.ptr) for x in xs])  # noqa: E731
         _check("xrs_gemm_batched", self.lib.xrs_gemm_batched(self.h, cnt, tab(Cs), M, N, alpha, tab(As), lda, int(transA),
                                                             K, tab(Bs), ldb, int(transB)))
+
+    def gemm_forms(self, Cs, M, N, alpha, As, lda, transA, K, Bs, ldb, transB, sym: bool = False, tri: int = 0):
+        """xrs_gemm_forms: the rounds' internal GEMM forms (symmetric batch, tri = 1 / 2 triangular skipping) over
+        lists of DeviceArrays; exposed for their tests."""
+        cnt = len(Cs)
+        tab = lambda xs: (_DP * max(1, cnt))(*[_DP(x.ptr) for x in xs])  # noqa: E731
+        _check("xrs_gemm_forms", self.lib.xrs_gemm_forms(self.h, cnt, tab(Cs), M, N, alpha, tab(As), lda, int(transA), K,
+                                                        tab(Bs), ldb, int(transB), int(sym), int(tri)))
 
     def tangent_to_tt(self, n, r, Us, Vs, add_base: bool):
         """xrs_tt_tangent_to_tt: the rank-2r block cores of a tangent vector (components Vs at the base Us, both

@@ -799,7 +799,7 @@ static void launch_glds(xrs_handle_t h, const PTR& P, int count, size_t lda, boo
         kdepth = s / tiles_m;
     } else if (tri & 2) {
         double s = 0;
-        for (int n0 = 0; n0 < N; n0 += BN) s += K - (n0 / BK) * BK;
+        for (int n0 = 0; n0 < N; n0 += BN) s += std::max(0, K - (n0 / BK) * BK);   // (N > K: columns with no K-step)
         kdepth = s / tiles_n;
     }
     KernelTimer timer(h, XRS_KFAM_GEMM, count * 2.0 * double(M) * double(N) * kdepth,
@@ -1132,5 +1132,31 @@ extern "C" int xrs_gemm_sym(xrs_handle_t h, double* C, size_t N, double alpha, c
         XRS_REQUIRE(C != A && C != B, "C must not alias A or B");
         xrs::fence_readers(h);
         xrs::gemm_sym(h, C, N, alpha, A, lda, transA != 0, K, B, ldb, transB != 0);
+    });
+}
+
+// The internal operand forms (symmetric batch, triangular skipping) behind one entry point, dispatched as the
+// rounds' gemm_grouped dispatches them; exposed for their tests.
+extern "C" int xrs_gemm_forms(xrs_handle_t h, size_t count, double* const* C, size_t M, size_t N, double alpha,
+                              const double* const* A, size_t lda, int transA, size_t K, const double* const* B,
+                              size_t ldb, int transB, int sym, int tri) {
+    return xrs::guarded([&] {
+        XRS_REQUIRE(h, "null handle");
+        XRS_REQUIRE(count == 0 || (A && B && C), "null pointer table");
+        XRS_REQUIRE(count < (1u << 20), "batch too large");
+        XRS_REQUIRE(tri == 0 || tri == xrs::kTriA || tri == xrs::kTriB, "tri must be 0, 1 (A lower) or 2 (B lower)");
+        XRS_REQUIRE(!sym || M == N, "symmetric result needs M == N");
+        XRS_REQUIRE(!sym || tri == 0, "sym and tri do not combine");
+        XRS_REQUIRE(transA ? lda >= M || K == 0 : lda >= K || M == 0, "lda too small");
+        XRS_REQUIRE(transB ? ldb >= K || N == 0 : ldb >= N || K == 0, "ldb too small");
+        for (size_t i = 0; i < count; ++i) {
+            XRS_REQUIRE(M == 0 || N == 0 || C[i], "null C");
+            XRS_REQUIRE(K == 0 || M == 0 || N == 0 || (A[i] && B[i]), "null A/B");
+            XRS_REQUIRE(C[i] != A[i] && C[i] != B[i], "C must not alias A or B");
+        }
+        xrs::fence_readers(h);
+        if (count == 1 && sym) xrs::gemm_sym(h, C[0], N, alpha, A[0], lda, transA != 0, K, B[0], ldb, transB != 0);
+        else if (count == 1) xrs::gemm(h, C[0], M, N, alpha, A[0], lda, transA != 0, K, B[0], ldb, transB != 0, tri);
+        else xrs::gemm_batched(h, int(count), C, M, N, alpha, A, lda, transA != 0, K, B, ldb, transB != 0, sym != 0, tri);
     });
 }
