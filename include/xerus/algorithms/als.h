@@ -5,6 +5,8 @@
 // Local systems are built from the cached left/right environments as dense tensors in HBM (each
 // environment update is one indexed product: permutations + MFMA GEMMs) and solved on the GPU
 // (xerus::solve: blocked Cholesky for the symmetric positive definite local operators of every variant).
+// The matrixFree variants (ALS_MF, ALS_SPD_MF; not in the reference) never build the local operator: they apply it
+// through the environments and the operator core and iterate (conjugate gradients on the device).
 #pragma once
 #include <functional>
 #include <utility>
@@ -62,6 +64,14 @@ class ALSVariant {
     bool preserveCorePosition;
     bool assumeSPD;
     LocalSolver localSolver;
+    /// Matrix-free local solve (single site, with an operator): the local operator is never assembled; it is
+    /// applied through the two environments and the operator core (xrs_als_local_apply) inside a conjugate-
+    /// gradient iteration that stays on the device (xrs_als_local_cg), started from the current component.
+    /// localSolver is not called. Deviation from the direct solve: the local system is solved to
+    /// localTolerance (relative residual), not to rounding.
+    bool matrixFree = false;
+    value_t localTolerance = 1e-12;
+    size_t localMaxIterations = 0;   ///< 0: the cap 4 N + 50, N the size of the component
 
     ALSVariant(unsigned _sites, size_t _numHalfSweeps, LocalSolver _localSolver, bool _assumeSPD, bool _useResidual = false);
 
@@ -88,12 +98,16 @@ class ALSVariant {
    private:
     Tensor construct_local_operator(const ALSAlgorithmicData& _data) const;
     Tensor construct_local_RHS(const ALSAlgorithmicData& _data) const;
+    void solve_local_matrix_free(ALSAlgorithmicData& _data) const;
     bool check_for_end_of_sweep(ALSAlgorithmicData& _data, size_t _numHalfSweeps, value_t _convergenceEpsilon) const;
 };
 
 /// the reference's predefined variants (als.cpp:556-563)
 extern const ALSVariant ALS;
 extern const ALSVariant ALS_SPD;
+/// ALS / ALS_SPD with matrixFree: ranks at which the dense local operator no longer fits
+extern const ALSVariant ALS_MF;
+extern const ALSVariant ALS_SPD_MF;
 /// two-site DMRG (merged component of two neighbours, split by an SVD truncated to the initial ranks)
 extern const ALSVariant DMRG;
 extern const ALSVariant DMRG_SPD;

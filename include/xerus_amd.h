@@ -426,6 +426,35 @@ int xrs_sketch_gaussian(xrs_handle_t handle, double* Y, size_t s, const double* 
 /** The route the handle's last xrs_sketch_gaussian took (XRS_SKETCH_*); 0 before the first. */
 int xrs_sketch_last_route(xrs_handle_t handle);
 
+/* ---------------------------------------------------------------- matrix-free ALS local problem (als.cpp:383-400) */
+/* The local operator M of a one-site ALS step, applied through its two environments and the operator core instead
+ * of being assembled ((rl n rr)^2 entries). All operands row-major; x, y, b are (rl, n, rr); A is the operator core
+ * (pl, n, n, pr).
+ *   normal == 0 (symmetric form, the environments of an SPD operator): L (rl, pl, rl), R (rr, pr, rr),
+ *     y(a,i,b) = sum L(a,p,a') A(p,i,j,q) R(b,q,b') x(a',j,b')
+ *   normal != 0 (A^T A, the normal equations): L (rl, pl, pl, rl), R (rr, pr, pr, rr),
+ *     y(a,i,b) = sum L(a,p,p',a') A(p,y,i,q) A(p',y,j,q') R(b,q,q',b') x(a',j,b')
+ * Null pointers or zero extents are XRS_EINVAL. Temporaries come from the handle's pool. */
+
+/** y = M x as a chain of three (normal: four) fp64 GEMMs; the only permutation is of the core (its two middle modes
+ *  swapped). y must not alias x. Enqueued only. */
+int xrs_als_local_apply(xrs_handle_t handle, double* y, const double* x, size_t rl, size_t n, size_t rr, size_t pl,
+                        size_t pr, const double* L, const double* A, const double* R, int normal);
+/** Conjugate gradients on M x = b from the start x (in: start, out: solution); M must be symmetric positive
+ *  definite. The iteration's scalars, its convergence flag and its counter stay in device memory; the host reads
+ *  them every check_every (>= 1) iterations and once at the start. Converged when ||r|| <= tol ||b|| (r the
+ *  recurrence residual); from then on the remaining launches change nothing, so x, *iters and *relres do not depend
+ *  on check_every. max_iter = 0 or above 4 N + 50 (N = rl n rr) means 4 N + 50. Reductions have a fixed order
+ *  (bit-reproducible). *status: XRS_CG_CONVERGED, XRS_CG_MAX_ITER (x = the last iterate) or XRS_CG_BREAKDOWN
+ *  (p^T M p <= 0 or not finite: x = the iterate before the failing update). *iters = updates applied, *relres =
+ *  ||r|| / ||b||. b = 0 gives x = 0 in 0 iterations. x must not alias b. tol >= 0. Synchronises. */
+#define XRS_CG_CONVERGED 0
+#define XRS_CG_MAX_ITER 1
+#define XRS_CG_BREAKDOWN 2
+int xrs_als_local_cg(xrs_handle_t handle, double* x, const double* b, size_t rl, size_t n, size_t rr, size_t pl,
+                     size_t pr, const double* L, const double* A, const double* R, int normal, double tol,
+                     size_t max_iter, size_t check_every, size_t* iters, double* relres, int* status);
+
 /* ---------------------------------------------------------------- profiling */
 /** Kernel-duration instrumentation: while enabled, every launch of a kernel whose family id is in
  *  `family_mask` is bracketed by HIP events on the handle's stream. */

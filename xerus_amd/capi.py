@@ -109,6 +109,9 @@ SIGNATURES = {
     "xrs_gaussian_matrix": (C.c_int, [_DP, _DP, _SZ, _SZ, C.c_uint64, C.c_uint32]),
     "xrs_sketch_gaussian": (C.c_int, [_DP, _DP, _SZ, _DP, _SZ, _SZ, C.c_uint64, C.c_uint32, C.c_int]),
     "xrs_sketch_last_route": (C.c_int, [_DP]),
+    "xrs_als_local_apply": (C.c_int, [_DP, _DP, _DP, _SZ, _SZ, _SZ, _SZ, _SZ, _DP, _DP, _DP, C.c_int]),
+    "xrs_als_local_cg": (C.c_int, [_DP, _DP, _DP, _SZ, _SZ, _SZ, _SZ, _SZ, _DP, _DP, _DP, C.c_int, C.c_double, _SZ, _SZ,
+                                   C.POINTER(_SZ), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "xrs_prof_begin": (C.c_int, [_DP, C.c_uint32]),
     "xrs_prof_end": (C.c_int, [_DP, C.POINTER(_SZ), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                C.POINTER(C.c_double)]),
@@ -477,6 +480,37 @@ class Handle:
     def sketch_last_route(self) -> str | None:
         """"fused" / "materialised": the route of this handle's last sketch_gaussian."""
         return SKETCH_ROUTES[self.lib.xrs_sketch_last_route(self.h)]
+
+    # ---- matrix-free ALS local problem (include/xerus_amd.h)
+    @staticmethod
+    def _local_extents(fn: str, dims, max_iter: int = 0, check_every: int = 1):
+        # the C types are size_t: ctypes would wrap a negative value silently
+        for v in (*dims, max_iter, check_every):
+            if not 0 <= int(v) < 2 ** 63:
+                raise XrsError(fn, -1, f"extent or count {v} is not a size")
+        return tuple(int(v) for v in dims)
+
+    def als_local_apply(self, y: "DeviceArray | None", x: "DeviceArray | None", dims, L: "DeviceArray | None",
+                        A: "DeviceArray | None", R: "DeviceArray | None", normal: bool):
+        """xrs_als_local_apply: y = M x for dims = (rl, n, rr, pl, pr); x, y (rl, n, rr), A (pl, n, n, pr), L / R the
+        environments ((r, p, r), normal: (r, p, p, r)). None passes a null pointer."""
+        rl, n, rr, pl, pr = self._local_extents("xrs_als_local_apply", dims)
+        ptr = lambda a: _DP(a.ptr) if a is not None else None  # noqa: E731
+        _check("xrs_als_local_apply", self.lib.xrs_als_local_apply(self.h, ptr(y), ptr(x), rl, n, rr, pl, pr, ptr(L), ptr(A),
+                                                                  ptr(R), int(bool(normal))))
+
+    def als_local_cg(self, x: "DeviceArray | None", b: "DeviceArray | None", dims, L: "DeviceArray | None",
+                     A: "DeviceArray | None", R: "DeviceArray | None", normal: bool, tol: float, max_iter: int = 0,
+                     check_every: int = 1):
+        """xrs_als_local_cg: CG on M x = b from the start in x (overwritten by the solution); returns
+        (iters, relres, status) with status 0 converged, 1 max_iter reached, 2 breakdown."""
+        rl, n, rr, pl, pr = self._local_extents("xrs_als_local_cg", dims, max_iter, check_every)
+        ptr = lambda a: _DP(a.ptr) if a is not None else None  # noqa: E731
+        iters, relres, status = _SZ(), C.c_double(), C.c_int()
+        _check("xrs_als_local_cg", self.lib.xrs_als_local_cg(self.h, ptr(x), ptr(b), rl, n, rr, pl, pr, ptr(L), ptr(A), ptr(R),
+                                                            int(bool(normal)), float(tol), int(max_iter), int(check_every),
+                                                            C.byref(iters), C.byref(relres), C.byref(status)))
+        return iters.value, relres.value, status.value
 
     def last_round_path(self) -> str | None:
         """"chain" / "truncate" / "general" / "reference": the algorithm of this handle's last TT round."""

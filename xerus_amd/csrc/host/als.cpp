@@ -10,7 +10,9 @@
 // the local systems are solved by xerus::solve (blocked Cholesky: all local operators here are
 // symmetric positive definite for SPD operators, and A^T A otherwise). Multi-site variants (DMRG: two
 // sites) optimise the merged component of `sites` neighbours and split it again with the indexed SVD
-// (lapack_solver, :43-69), truncated to the initial ranks.
+// (lapack_solver, :43-69), truncated to the initial ranks. With ALSVariant::matrixFree (ALS_MF, ALS_SPD_MF) the
+// local operator is not assembled: solve_local_matrix_free runs xrs_als_local_cg (als_local.hip) on the
+// environments, the operator core and the local right-hand side.
 //
 // Deviation: in the reference's move_to_next_index the decreasing direction extends the right stacks by
 // the slice of currIndex (als.cpp:371-379), which is the site that enters the next window when sites > 1
@@ -19,7 +21,9 @@
 // environment for DMRG (checked against dense solutions and the oracle's restatement, which makes the
 // same choice).
 #include <cmath>
+#include <cstdio>
 
+#include "xerus_amd.h"   // (before xerus.h: gpu::handle() returns the C-ABI's handle type)
 #include "xerus.h"
 #include "xerus/algorithms/als.h"
 
@@ -341,6 +345,43 @@ Tensor ALSVariant::construct_local_RHS(const ALSAlgorithmicData& _data) const {
     return res;
 }
 
+// matrix-free local solve (matrixFree): CG on the local system, the operator applied through opLeft.back(), the
+// operator core and opRight.back() (xrs_als_local_cg), started from the current component. The tensors' lazy
+// factors are applied into copies first (copy-on-write: no copy where the factor is 1).
+void ALSVariant::solve_local_matrix_free(ALSAlgorithmicData& _data) const {
+    const size_t c = _data.currIndex;
+    Tensor L = _data.opLeft.back(), R = _data.opRight.back(), Ak = _data.A->get_component(c);
+    Tensor rhs = construct_local_RHS(_data);
+    Tensor xk = _data.x.get_component(c);
+    const size_t rl = xk.dimensions[0], n = xk.dimensions[1], rr = xk.dimensions[2];
+    const size_t pl = Ak.dimensions[0], pr = Ak.dimensions[3];
+    const auto applied = [](Tensor& _t) {
+        _t.apply_factor();
+        return _t.device_data();
+    };
+    const double* Ld = applied(L);
+    const double* Ad = applied(Ak);
+    const double* Rd = applied(R);
+    const double* bd = applied(rhs);
+    double* xd = xk.device_data_applied();
+    size_t iters = 0;
+    double relres = 0.0;
+    int status = 0;
+    const int st = xrs_als_local_cg(gpu::handle(), xd, bd, rl, n, rr, pl, pr, Ld, Ad, Rd, assumeSPD ? 0 : 1, localTolerance,
+                                    localMaxIterations, 16, &iters, &relres, &status);
+    if (st != XRS_OK) throw misc::generic_error(xrs_last_error());
+    if (status == XRS_CG_BREAKDOWN) {
+        throw misc::generic_error() << "matrix-free ALS: the local operator at site " << c
+                                    << " is not positive definite (CG broke down after " << iters
+                                    << " iterations); the SPD variants need a symmetric positive definite operator";
+    }
+    if (status == XRS_CG_MAX_ITER) {
+        std::fprintf(stderr, "[xerus_amd warning] matrix-free ALS: CG at site %zu stopped after %zu iterations at relative residual %.3e (tolerance %.3e)\n",
+                     c, iters, relres, double(localTolerance));
+    }
+    _data.x.set_component(c, std::move(xk));
+}
+
 bool ALSVariant::check_for_end_of_sweep(ALSAlgorithmicData& _data, size_t _numHalfSweeps, value_t _convergenceEpsilon) const {
     const bool atEnd = (_data.direction == Decreasing && _data.currIndex == _data.optimizedRange.first) ||
                        (_data.direction == Increasing && _data.currIndex == _data.optimizedRange.second - sites);
@@ -372,10 +413,13 @@ double ALSVariant::solve(const TTOperator* _Ap, TTTensor& _x, const TTTensor& _b
             XERUS_REQUIRE(_Ap->dimensions[i + _Ap->degree() / 2] == _x.dimensions[i], "");
         }
     }
+    XERUS_REQUIRE(!(matrixFree && _Ap) || sites == 1, "the matrix-free local solve is defined for single site alternation only");
     ALSAlgorithmicData data(*this, _Ap, _x, _b);
     data.energy = data.energy_f();
     while (true) {
-        if (_Ap) {
+        if (_Ap && matrixFree) {
+            solve_local_matrix_free(data);
+        } else if (_Ap) {
             std::vector<Tensor> tmpX;
             for (size_t p = 0; p < sites; ++p) tmpX.push_back(_x.get_component(data.currIndex + p));
             localSolver(construct_local_operator(data), tmpX, construct_local_RHS(data), data);
@@ -391,6 +435,14 @@ double ALSVariant::solve(const TTOperator* _Ap, TTTensor& _x, const TTTensor& _b
 
 const ALSVariant ALS(1, 0, ALSVariant::lapack_solver, false);
 const ALSVariant ALS_SPD(1, 0, ALSVariant::lapack_solver, true);
+namespace {
+ALSVariant matrix_free(ALSVariant _variant) {
+    _variant.matrixFree = true;
+    return _variant;
+}
+}  // namespace
+const ALSVariant ALS_MF = matrix_free(ALSVariant(1, 0, ALSVariant::lapack_solver, false));
+const ALSVariant ALS_SPD_MF = matrix_free(ALSVariant(1, 0, ALSVariant::lapack_solver, true));
 const ALSVariant DMRG(2, 0, ALSVariant::lapack_solver, false);
 const ALSVariant DMRG_SPD(2, 0, ALSVariant::lapack_solver, true);
 const ALSVariant ASD(1, 0, ALSVariant::ASD_solver, false);

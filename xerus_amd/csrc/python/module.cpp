@@ -392,6 +392,9 @@ PYBIND11_MODULE(xerus, m) {
         .def_readwrite("useResidualForEndCriterion", &ALSVariant::useResidualForEndCriterion)
         .def_readwrite("preserveCorePosition", &ALSVariant::preserveCorePosition)
         .def_readwrite("assumeSPD", &ALSVariant::assumeSPD)
+        .def_readwrite("matrixFree", &ALSVariant::matrixFree)
+        .def_readwrite("localTolerance", &ALSVariant::localTolerance)
+        .def_readwrite("localMaxIterations", &ALSVariant::localMaxIterations)
         .def("__call__", [](const ALSVariant& _s, const TTOperator& _A, TTTensor& _x, const TTTensor& _b, value_t _eps) {
             return _s(_A, _x, _b, _eps);
         })
@@ -405,6 +408,8 @@ PYBIND11_MODULE(xerus, m) {
         .def("__copy__", [](const ALSVariant& _s) { return ALSVariant(_s); });
     m.attr("ALS") = py::cast(ALSVariant(ALS));
     m.attr("ALS_SPD") = py::cast(ALSVariant(ALS_SPD));
+    m.attr("ALS_MF") = py::cast(ALSVariant(ALS_MF));
+    m.attr("ALS_SPD_MF") = py::cast(ALSVariant(ALS_SPD_MF));
     m.attr("DMRG") = py::cast(ALSVariant(DMRG));
     m.attr("DMRG_SPD") = py::cast(ALSVariant(DMRG_SPD));
     m.attr("ASD") = py::cast(ALSVariant(ASD));

@@ -53,7 +53,8 @@ constexpr Region kHostResult{0, 64, "a scalar result or up to 16 status words"};
 constexpr Region kHostOrthEmax{64, 64, "orthogonalize: the 8 partial maxima of its first-order pass"};
 constexpr Region kHostIdentityDev{256, 8, "max_abs_dev_identity"};
 constexpr Region kHostAmax{384, 8, "range_exponent: max |A|"};
-constexpr Region kHostLocalSlots[] = {kHostResult, kHostOrthEmax, kHostIdentityDev, kHostAmax};
+constexpr Region kHostCgState{128, 64, "als_local_cg: the iteration's state words (CgState)"};
+constexpr Region kHostLocalSlots[] = {kHostResult, kHostOrthEmax, kHostCgState, kHostIdentityDev, kHostAmax};
 static_assert(disjoint_within(kHostLocalSlots, kHostLocal.off, kHostLocal.off + kHostLocal.len));
 constexpr Region kHostChainDev{512, 8192, "chain_check: (d - 1) x 16 orthonormality deviations"};
 constexpr Region kHostSvdCheck{640, 40, "svd_bidiag: residuals (4 doubles) and the multisection status"};
@@ -67,7 +68,10 @@ constexpr Region kDevAmax{384, 8, "range_exponent: max |A|"};
 constexpr Region kDevRangeAmax{392, 8, "range_controlled: max |A|"};
 constexpr Region kDevPartials{512, 24576, "reduce_to_device: 3 x 1024 partial sums"};
 constexpr Region kDevRangeProbe{32768, 7680, "probe_core_ranges: one norm per core (<= 960)"};
-constexpr Region kDevMap[] = {kDevResult, kDevIdentityDev, kDevOrthEmax, kDevAmax, kDevRangeAmax, kDevPartials, kDevRangeProbe};
+constexpr Region kDevCgState{40960, 64, "als_local_cg: rr, rr_prev, pq, ||b||^2, threshold; done, skip, status, iterations"};
+constexpr Region kDevCgPartials{45056, 16384, "als_local_cg: 2 x 1024 partial sums (p.q / b.b and r.r)"};
+constexpr Region kDevMap[] = {kDevResult,    kDevIdentityDev, kDevOrthEmax, kDevAmax,      kDevRangeAmax,
+                              kDevPartials, kDevRangeProbe,  kDevCgState,  kDevCgPartials};
 static_assert(disjoint_within(kDevMap, 0, kBytes), "device scratch regions overlap or leave the allocation");
 
 template <class T>
