@@ -10,6 +10,7 @@
 #include "xerus/tensorNetwork.h"
 #include "xerus/ttNetwork.h"
 #include "xerus/algorithms/als.h"
+#include "xerus/algorithms/alsEigen.h"
 #include "xerus/algorithms/retractions.h"
 #include "xerus/algorithms/steepestDescent.h"
 #include "xerus/algorithms/cg.h"

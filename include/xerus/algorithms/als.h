@@ -102,6 +102,14 @@ class ALSVariant {
     bool check_for_end_of_sweep(ALSAlgorithmicData& _data, size_t _numHalfSweeps, value_t _convergenceEpsilon) const;
 };
 
+namespace internal {
+/// One step of the symmetric-form operator environments <x, A x> (3 modes: x rank, operator rank, x rank), one
+/// indexed product each: the left environment extended over site component _xk / operator component _Ak, and the
+/// mirror image. Shared by ALSVariant (assumeSPD) and ALSEigenVariant.
+Tensor als_env_step_left(const Tensor& _env, const Tensor& _xk, const Tensor& _Ak);
+Tensor als_env_step_right(const Tensor& _env, const Tensor& _xk, const Tensor& _Ak);
+}  // namespace internal
+
 /// the reference's predefined variants (als.cpp:556-563)
 extern const ALSVariant ALS;
 extern const ALSVariant ALS_SPD;

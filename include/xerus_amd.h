@@ -455,6 +455,30 @@ int xrs_als_local_cg(xrs_handle_t handle, double* x, const double* b, size_t rl,
                      size_t pr, const double* L, const double* A, const double* R, int normal, double tol,
                      size_t max_iter, size_t check_every, size_t* iters, double* relres, int* status);
 
+/** The smallest algebraic eigenvalue of M (symmetric form, normal == 0 above; M must be symmetric) and its unit
+ *  eigenvector by LOBPCG with block size 1 and no preconditioner: x (in: start, out: eigenvector, ||x|| = 1), *theta
+ *  = x^T M x. One operator application per iteration; the iteration's scalars, its convergence flag and its counter
+ *  stay in device memory, and the host reads them every check_every (>= 1) iterations and once after the
+ *  initialisation. Converged when ||M x - theta x|| <= tol ||M x0||, x0 the normalised start (the threshold is fixed
+ *  at the start, so a start that is an eigenvector takes 0 iterations); from then on the remaining launches change
+ *  nothing, so x, *theta, *iters and *relres do not depend on check_every. max_iter = 0 or above 4 N + 50 (N = rl n
+ *  rr) means 4 N + 50. Reductions have a fixed order (bit-reproducible). *status: XRS_EIG_CONVERGED, XRS_EIG_MAX_ITER
+ *  (x = the last iterate) or XRS_EIG_BREAKDOWN (the 3 x 3 problem of a step could not be solved, or a value is not
+ *  finite: x = the iterate before the failing step; a zero or non-finite start and non-finite operands end so with
+ *  *iters = 0). *relres = ||r|| / ||M x0||. tol >= 0 and finite, else XRS_EINVAL. Synchronises. */
+#define XRS_EIG_CONVERGED 0
+#define XRS_EIG_MAX_ITER 1
+#define XRS_EIG_BREAKDOWN 2
+int xrs_als_local_eig(xrs_handle_t handle, double* x, size_t rl, size_t n, size_t rr, size_t pl, size_t pr,
+                      const double* L, const double* A, const double* R, double tol, size_t max_iter, size_t check_every,
+                      double* theta, size_t* iters, double* relres, int* status);
+/** Host only, no GPU: the smallest pair (*theta, c[0..k-1]) of the k x k (k = 2, 3) pencil H c = theta G c given by the
+ *  upper triangles of G (positive definite) and H, row by row -- the small problem of one xrs_als_local_eig step, with
+ *  its pivot rule: G is scaled to unit diagonal and Cholesky-factored; a squared pivot below 1e-8 drops the last basis
+ *  vector. c has unit G-norm and c[0] >= 0. Returns the number of basis vectors used (k, or k - 1 after dropping the
+ *  last: then c[k-1] = 0), 0 on breakdown or illegal arguments (*theta, c untouched). */
+int xrs_geneig_lowest(int k, const double* G, const double* H, double* theta, double* c);
+
 /* ---------------------------------------------------------------- profiling */
 /** Kernel-duration instrumentation: while enabled, every launch of a kernel whose family id is in
  *  `family_mask` is bracketed by HIP events on the handle's stream. */

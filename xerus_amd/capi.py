@@ -112,6 +112,10 @@ SIGNATURES = {
     "xrs_als_local_apply": (C.c_int, [_DP, _DP, _DP, _SZ, _SZ, _SZ, _SZ, _SZ, _DP, _DP, _DP, C.c_int]),
     "xrs_als_local_cg": (C.c_int, [_DP, _DP, _DP, _SZ, _SZ, _SZ, _SZ, _SZ, _DP, _DP, _DP, C.c_int, C.c_double, _SZ, _SZ,
                                    C.POINTER(_SZ), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "xrs_als_local_eig": (C.c_int, [_DP, _DP, _SZ, _SZ, _SZ, _SZ, _SZ, _DP, _DP, _DP, C.c_double, _SZ, _SZ,
+                                    C.POINTER(C.c_double), C.POINTER(_SZ), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "xrs_geneig_lowest": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                    C.POINTER(C.c_double)]),
     "xrs_prof_begin": (C.c_int, [_DP, C.c_uint32]),
     "xrs_prof_end": (C.c_int, [_DP, C.POINTER(_SZ), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                C.POINTER(C.c_double)]),
@@ -159,6 +163,18 @@ def _check(fn: str, status: int):
 def svd_batched_fits(m: int, n: int) -> bool:
     """Whether Handle.svd_batched factors m x n members in its batched kernel (else one by one); needs no GPU."""
     return bool(load().xrs_svd_batched_fits(int(m), int(n)))
+
+
+def geneig_lowest(k: int, G: Sequence[float], H: Sequence[float]):
+    """xrs_geneig_lowest: the smallest pair of the k x k (k = 2, 3) pencil given by its upper triangles; returns
+    (used, theta, c) with used = k, k - 1 after dropping the last basis vector, or 0 on breakdown. Needs no GPU."""
+    m = k * (k + 1) // 2
+    if k not in (2, 3) or len(G) != m or len(H) != m:
+        raise XrsError("xrs_geneig_lowest", -1, f"k = {k} needs {m} entries of each upper triangle")
+    g, h = (C.c_double * m)(*[float(v) for v in G]), (C.c_double * m)(*[float(v) for v in H])
+    theta, c = C.c_double(), (C.c_double * 3)()
+    used = load().xrs_geneig_lowest(k, g, h, C.byref(theta), c)
+    return used, theta.value, np.array(c[:k])
 
 
 def _arr(vals: Sequence[int]):
@@ -511,6 +527,19 @@ class Handle:
                                                             int(bool(normal)), float(tol), int(max_iter), int(check_every),
                                                             C.byref(iters), C.byref(relres), C.byref(status)))
         return iters.value, relres.value, status.value
+
+    def als_local_eig(self, x: "DeviceArray | None", dims, L: "DeviceArray | None", A: "DeviceArray | None",
+                      R: "DeviceArray | None", tol: float, max_iter: int = 0, check_every: int = 1):
+        """xrs_als_local_eig: the smallest eigenvalue of the symmetric-form M from the start in x (overwritten by the
+        unit eigenvector); returns (theta, iters, relres, status) with status 0 converged, 1 max_iter reached,
+        2 breakdown."""
+        rl, n, rr, pl, pr = self._local_extents("xrs_als_local_eig", dims, max_iter, check_every)
+        ptr = lambda a: _DP(a.ptr) if a is not None else None  # noqa: E731
+        theta, iters, relres, status = C.c_double(), _SZ(), C.c_double(), C.c_int()
+        _check("xrs_als_local_eig", self.lib.xrs_als_local_eig(self.h, ptr(x), rl, n, rr, pl, pr, ptr(L), ptr(A), ptr(R),
+                                                              float(tol), int(max_iter), int(check_every), C.byref(theta),
+                                                              C.byref(iters), C.byref(relres), C.byref(status)))
+        return theta.value, iters.value, relres.value, status.value
 
     def last_round_path(self) -> str | None:
         """"chain" / "truncate" / "general" / "reference": the algorithm of this handle's last TT round."""

@@ -23,6 +23,7 @@
 #include <cmath>
 
 #include "als_local.hpp"
+#include "als_reduce.hpp"
 #include "elementwise.hpp"
 #include "scratch_map.hpp"
 
@@ -31,36 +32,12 @@ namespace als_local {
 
 namespace {
 
-constexpr int CB = 256;       // threads per block
-constexpr int CMAXB = 1024;   // max blocks (= partial sums per reduction)
-
 struct CgState {
     double rr, rr_prev, pq, bb, thresh;
     int done, skip, status, iters;
 };
 static_assert(sizeof(CgState) <= scratch::kDevCgState.len && sizeof(CgState) <= scratch::kHostCgState.len);
 static_assert(2 * CMAXB * sizeof(double) <= scratch::kDevCgPartials.len);
-
-// the block's sum, in every thread
-__device__ __forceinline__ double block_sum_all(double v) {
-    __shared__ double part[CB / 64];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-#pragma unroll
-    for (int i = 0; i < CB / 64; ++i) s += part[i];
-    __syncthreads();
-    return s;
-}
-
-// the sum of nb block partials, in every thread of every block in the same order
-__device__ __forceinline__ double sum_partials(const double* __restrict__ partial, int nb) {
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < nb; i += CB) acc += partial[i];
-    return block_sum_all(acc);
-}
 
 // r = b - q (q = M x0), p = r; partial sums of r.r (first CMAXB) and b.b (second CMAXB)
 __global__ void __launch_bounds__(CB) k_cg_init(double* __restrict__ r, double* __restrict__ p, const double* __restrict__ b,
@@ -169,8 +146,6 @@ __global__ void __launch_bounds__(CB) k_cg_direction(const double* __restrict__ 
         }
     }
 }
-
-int blocks_for(size_t n) { return int(std::max<size_t>(1, std::min<size_t>(CMAXB, (n + size_t(CB) * 4 - 1) / (size_t(CB) * 4)))); }
 
 CgState read_state(xrs_handle_t h, const CgState* dev) {
     CgState* host = scratch::host<CgState>(h, scratch::kHostCgState);

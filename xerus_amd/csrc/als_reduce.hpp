@@ -1,0 +1,40 @@
+// Device helpers shared by the iterations on the local operator (als_local.hip: CG, als_eig.hip: LOBPCG): the
+// launch shape of their vector kernels and the fixed-order sums that make every block hold the same scalar without a
+// grid barrier or a floating-point atomic.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstddef>
+
+namespace xrs {
+namespace als_local {
+
+constexpr int CB = 256;       // threads per block
+constexpr int CMAXB = 1024;   // max blocks (= partial sums per reduction)
+
+// the block's sum, in every thread
+__device__ __forceinline__ double block_sum_all(double v) {
+    __shared__ double part[CB / 64];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < CB / 64; ++i) s += part[i];
+    __syncthreads();
+    return s;
+}
+
+// the sum of nb block partials, in every thread of every block in the same order
+__device__ __forceinline__ double sum_partials(const double* __restrict__ partial, int nb) {
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < nb; i += CB) acc += partial[i];
+    return block_sum_all(acc);
+}
+
+inline int blocks_for(size_t n) { return int(std::max<size_t>(1, std::min<size_t>(CMAXB, (n + size_t(CB) * 4 - 1) / (size_t(CB) * 4)))); }
+
+}  // namespace als_local
+}  // namespace xrs

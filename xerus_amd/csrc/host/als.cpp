@@ -150,13 +150,29 @@ void ALSVariant::ALSAlgorithmicData::prepare_x_for_als() {
 
 // environment updates (the reference's localOperatorSlice / localRhsSlice contracted into the stack,
 // :190-223, 240-256): one product each
+namespace internal {
+Tensor als_env_step_left(const Tensor& _env, const Tensor& _xk, const Tensor& _Ak) {
+    Index r1, r2, r3, c1, c2, c3, n1, n2;
+    Tensor res;
+    res(c1, c2, c3) = _env(r1, r2, r3) * _xk(r1, n1, c1) * _Ak(r2, n1, n2, c2) * _xk(r3, n2, c3);
+    return res;
+}
+
+Tensor als_env_step_right(const Tensor& _env, const Tensor& _xk, const Tensor& _Ak) {
+    Index r1, r2, r3, c1, c2, c3, n1, n2;
+    Tensor res;
+    res(r1, r2, r3) = _xk(r1, n1, c1) * _Ak(r2, n1, n2, c2) * _xk(r3, n2, c3) * _env(c1, c2, c3);
+    return res;
+}
+}  // namespace internal
+
 Tensor ALSVariant::ALSAlgorithmicData::op_step_left(const Tensor& _env, size_t _pos) const {
     Index r1, r2, r3, r4, c1, c2, c3, c4, n1, n2, n3;
     const Tensor& xk = x.get_component(_pos);
     const Tensor& Ak = A->get_component(_pos);
+    if (ALS.assumeSPD) return internal::als_env_step_left(_env, xk, Ak);
     Tensor res;
-    if (ALS.assumeSPD) res(c1, c2, c3) = _env(r1, r2, r3) * xk(r1, n1, c1) * Ak(r2, n1, n2, c2) * xk(r3, n2, c3);
-    else res(c1, c2, c3, c4) = _env(r1, r2, r3, r4) * xk(r1, n1, c1) * Ak(r2, n2, n1, c2) * Ak(r3, n2, n3, c3) * xk(r4, n3, c4);
+    res(c1, c2, c3, c4) = _env(r1, r2, r3, r4) * xk(r1, n1, c1) * Ak(r2, n2, n1, c2) * Ak(r3, n2, n3, c3) * xk(r4, n3, c4);
     return res;
 }
 
@@ -164,9 +180,9 @@ Tensor ALSVariant::ALSAlgorithmicData::op_step_right(const Tensor& _env, size_t 
     Index r1, r2, r3, r4, c1, c2, c3, c4, n1, n2, n3;
     const Tensor& xk = x.get_component(_pos);
     const Tensor& Ak = A->get_component(_pos);
+    if (ALS.assumeSPD) return internal::als_env_step_right(_env, xk, Ak);
     Tensor res;
-    if (ALS.assumeSPD) res(r1, r2, r3) = xk(r1, n1, c1) * Ak(r2, n1, n2, c2) * xk(r3, n2, c3) * _env(c1, c2, c3);
-    else res(r1, r2, r3, r4) = xk(r1, n1, c1) * Ak(r2, n2, n1, c2) * Ak(r3, n2, n3, c3) * xk(r4, n3, c4) * _env(c1, c2, c3, c4);
+    res(r1, r2, r3, r4) = xk(r1, n1, c1) * Ak(r2, n2, n1, c2) * Ak(r3, n2, n3, c3) * xk(r4, n3, c4) * _env(c1, c2, c3, c4);
     return res;
 }
 

@@ -415,6 +415,19 @@ PYBIND11_MODULE(xerus, m) {
     m.attr("ASD") = py::cast(ALSVariant(ASD));
     m.attr("ASD_SPD") = py::cast(ALSVariant(ASD_SPD));
 
+    // ------------------------------------------------------------------ lowest eigenpair (algorithms/alsEigen.h)
+    py::class_<ALSEigenVariant>(m, "ALSEigenVariant")
+        .def_readwrite("numHalfSweeps", &ALSEigenVariant::numHalfSweeps)
+        .def_readwrite("convergenceEpsilon", &ALSEigenVariant::convergenceEpsilon)
+        .def_readwrite("preserveCorePosition", &ALSEigenVariant::preserveCorePosition)
+        .def_readwrite("localTolerance", &ALSEigenVariant::localTolerance)
+        .def_readwrite("localMaxIterations", &ALSEigenVariant::localMaxIterations)
+        .def("__call__", [](const ALSEigenVariant& _s, const TTOperator& _A, TTTensor& _x, value_t _eps) { return _s(_A, _x, _eps); })
+        .def("__call__", [](const ALSEigenVariant& _s, const TTOperator& _A, TTTensor& _x, size_t _n) { return _s(_A, _x, _n); })
+        .def("__call__", [](const ALSEigenVariant& _s, const TTOperator& _A, TTTensor& _x) { return _s(_A, _x); })
+        .def("__copy__", [](const ALSEigenVariant& _s) { return ALSEigenVariant(_s); });
+    m.attr("ALS_EIGEN") = py::cast(ALSEigenVariant(ALS_EIGEN));
+
     // ------------------------------------------------------------------ Riemannian optimisation
     // (algorithms/retractions.h, steepestDescent.h, cg.h)
     py::class_<TTTangentVector>(m, "TTTangentVector")

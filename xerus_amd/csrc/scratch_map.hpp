@@ -54,7 +54,8 @@ constexpr Region kHostOrthEmax{64, 64, "orthogonalize: the 8 partial maxima of i
 constexpr Region kHostIdentityDev{256, 8, "max_abs_dev_identity"};
 constexpr Region kHostAmax{384, 8, "range_exponent: max |A|"};
 constexpr Region kHostCgState{128, 64, "als_local_cg: the iteration's state words (CgState)"};
-constexpr Region kHostLocalSlots[] = {kHostResult, kHostOrthEmax, kHostCgState, kHostIdentityDev, kHostAmax};
+constexpr Region kHostEigState{192, 64, "als_local_eig: the iteration's state words (EigState)"};
+constexpr Region kHostLocalSlots[] = {kHostResult, kHostOrthEmax, kHostCgState, kHostEigState, kHostIdentityDev, kHostAmax};
 static_assert(disjoint_within(kHostLocalSlots, kHostLocal.off, kHostLocal.off + kHostLocal.len));
 constexpr Region kHostChainDev{512, 8192, "chain_check: (d - 1) x 16 orthonormality deviations"};
 constexpr Region kHostSvdCheck{640, 40, "svd_bidiag: residuals (4 doubles) and the multisection status"};
@@ -69,9 +70,10 @@ constexpr Region kDevRangeAmax{392, 8, "range_controlled: max |A|"};
 constexpr Region kDevPartials{512, 24576, "reduce_to_device: 3 x 1024 partial sums"};
 constexpr Region kDevRangeProbe{32768, 7680, "probe_core_ranges: one norm per core (<= 960)"};
 constexpr Region kDevCgState{40960, 64, "als_local_cg: rr, rr_prev, pq, ||b||^2, threshold; done, skip, status, iterations"};
+constexpr Region kDevEigState{41024, 64, "als_local_eig: theta, theta_next, rr, ||M x0||^2, threshold; done, skip, status, iterations"};
 constexpr Region kDevCgPartials{45056, 16384, "als_local_cg: 2 x 1024 partial sums (p.q / b.b and r.r)"};
 constexpr Region kDevMap[] = {kDevResult,    kDevIdentityDev, kDevOrthEmax, kDevAmax,      kDevRangeAmax,
-                              kDevPartials, kDevRangeProbe,  kDevCgState,  kDevCgPartials};
+                              kDevPartials, kDevRangeProbe,  kDevCgState,  kDevEigState,   kDevCgPartials};
 static_assert(disjoint_within(kDevMap, 0, kBytes), "device scratch regions overlap or leave the allocation");
 
 template <class T>
