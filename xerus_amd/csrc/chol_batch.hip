@@ -222,7 +222,8 @@ int chol_status_count(const std::vector<CholJob>& jobs) {
 
 // Status layout: one word per n <= 256 job in job order, then two per 257..512 job, then the blocks of the
 // larger ones.
-void chol_enqueue(xrs_handle_t h, const std::vector<CholJob>& jobs, int* status, std::vector<DevBuf>& keep) {
+void chol_enqueue_factors(xrs_handle_t h, const std::vector<CholJob>& jobs, int* status, std::vector<DevBuf>& keep,
+                          CholInverses& later) {
     std::vector<const CholJob*> small, huge;
     std::vector<BigJob> big;
     size_t dsz = 0;
@@ -255,8 +256,7 @@ void chol_enqueue(xrs_handle_t h, const std::vector<CholJob>& jobs, int* status,
     if (ns == 0) return;
     keep.emplace_back(h, dsz * 8);   // the diagonal-block inverses of every n <= 256 job: one slab per call
     double* dinv = keep.back().d();
-    struct Inverse { const double* L; const double* Dinv; double* X; int n; };
-    std::vector<Inverse> inv;   // the factor jobs that ask for Z
+    std::vector<CholInverses::Item>& inv = later.items;   // the factor jobs that ask for Z
     for (int b0 = 0; b0 < ns; b0 += kPotrfBatchMax) {
         PotrfBatch pb{};
         const int c = std::min(kPotrfBatchMax, ns - b0);
@@ -273,11 +273,15 @@ void chol_enqueue(xrs_handle_t h, const std::vector<CholJob>& jobs, int* status,
         pb.status = status + b0;
         potrf_batched(h, pb, c);
     }
+}
+
+void chol_enqueue_inverses(xrs_handle_t h, const CholInverses& later) {
+    const std::vector<CholInverses::Item>& inv = later.items;
     for (size_t b0 = 0; b0 < inv.size(); b0 += kTrinvBatchMax) {
         TrinvBatch tb{};
         const int c = int(std::min<size_t>(kTrinvBatchMax, inv.size() - b0));
         for (int i = 0; i < c; ++i) {
-            const Inverse& v = inv[b0 + size_t(i)];
+            const CholInverses::Item& v = inv[b0 + size_t(i)];
             tb.L[i] = v.L;
             tb.Dinv[i] = v.Dinv;
             tb.X[i] = v.X;
@@ -285,6 +289,12 @@ void chol_enqueue(xrs_handle_t h, const std::vector<CholJob>& jobs, int* status,
         }
         trinv_batched(h, tb, c);
     }
+}
+
+void chol_enqueue(xrs_handle_t h, const std::vector<CholJob>& jobs, int* status, std::vector<DevBuf>& keep) {
+    CholInverses later;
+    chol_enqueue_factors(h, jobs, status, keep, later);
+    chol_enqueue_inverses(h, later);
 }
 
 }  // namespace xrs

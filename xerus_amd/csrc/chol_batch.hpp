@@ -34,4 +34,22 @@ int chol_status_count(const std::vector<CholJob>& jobs);
 // but the callers claim nothing about them.
 void chol_enqueue(xrs_handle_t h, const std::vector<CholJob>& jobs, int* status, std::vector<DevBuf>& keep);
 
+// The same in two calls, for a caller that runs the explicit inverses on another lane than the factorisations
+// (tt.hip chain_pass): chol_enqueue_factors enqueues everything but the inverse launches of the n <= 256 jobs
+// and lists those in `later`; chol_enqueue_inverses enqueues them on the handle's (then current) stream, which
+// the caller has ordered behind the factorisations. The inverses read L and the diagonal-block slab in `keep`:
+// both outlive them. Jobs above 256 get their Z in the first call, as part of their blocked factorisation.
+struct CholInverses {
+    struct Item {
+        const double* L;
+        const double* Dinv;
+        double* X;
+        int n;
+    };
+    std::vector<Item> items;
+};
+void chol_enqueue_factors(xrs_handle_t h, const std::vector<CholJob>& jobs, int* status, std::vector<DevBuf>& keep,
+                          CholInverses& later);
+void chol_enqueue_inverses(xrs_handle_t h, const CholInverses& later);
+
 }  // namespace xrs

@@ -185,6 +185,16 @@ void StreamFork::join() {
     for (int i = 0; i < sides_; ++i) stream_signal(h_->side_stream[i], main_stream_, h_->ev_join[i]);
 }
 
+void StreamFork::mark_side(int i) {
+    if (h_->prof_mask) return;
+    XRS_HIP(hipEventRecord(h_->ev_aux, h_->side_stream[i]));
+}
+
+void StreamFork::main_wait_mark() {
+    if (h_->prof_mask) return;
+    XRS_HIP(hipStreamWaitEvent(main_stream_, h_->ev_aux, 0));
+}
+
 StreamFork::~StreamFork() {
     try {
         join();

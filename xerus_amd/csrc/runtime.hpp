@@ -217,6 +217,12 @@ class StreamFork {
     void lane(int i);       // 0 = main stream, 1..sides = side stream i-1 (round-robin helper)
     void main();            // switch back
     void join();            // main stream waits for every side stream's work
+    // One dependency of the main stream on a point inside side stream i, without ending the fork:
+    // mark_side() records that point (ev_aux) and main_wait_mark() lets the main stream wait for it from
+    // wherever it has got to by then. Both do nothing while the lanes are serialised (xrs_prof_begin):
+    // program order on the main stream is the dependency then.
+    void mark_side(int i = 0);
+    void main_wait_mark();
     int lanes() const { return sides_ + 1; }
    private:
     xrs_handle_t h_;

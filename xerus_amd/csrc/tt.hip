@@ -21,6 +21,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <limits>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <cstdio>
@@ -346,6 +347,31 @@ __global__ void __launch_bounds__(256) k_dev_identity_many(const DevIdArgs args)
 void rl_sweep(TT& t, const size_t* max_ranks, double eps, double cX, size_t from);
 
 
+static bool same_shape(const GemmJob& o, const GemmJob& g) {
+    return o.M == g.M && o.N == g.N && o.K == g.K && o.lda == g.lda && o.ldb == g.ldb && o.ta == g.ta && o.tb == g.tb &&
+           o.sym == g.sym && o.alpha == g.alpha && o.tri == g.tri;
+}
+
+std::vector<bool> largest_group(const std::vector<GemmJob>& jobs) {
+    std::vector<bool> done(jobs.size(), false), best(jobs.size(), false);
+    double best_flops = -1.0;
+    for (size_t i = 0; i < jobs.size(); ++i) {
+        if (done[i]) continue;
+        std::vector<bool> mine(jobs.size(), false);
+        double flops = 0.0;
+        for (size_t j = i; j < jobs.size(); ++j) {
+            if (done[j] || !same_shape(jobs[j], jobs[i])) continue;
+            done[j] = mine[j] = true;
+            flops += double(jobs[j].M) * double(jobs[j].N) * double(jobs[j].K);
+        }
+        if (flops > best_flops) {
+            best_flops = flops;
+            best = mine;
+        }
+    }
+    return best;
+}
+
 // Independent GEMMs; the ones of identical shape go out as one batched launch.
 void gemm_grouped(xrs_handle_t h, const std::vector<GemmJob>& jobs) {
     std::vector<bool> done(jobs.size(), false);
@@ -356,8 +382,7 @@ void gemm_grouped(xrs_handle_t h, const std::vector<GemmJob>& jobs) {
         std::vector<double*> C;
         for (size_t j = i; j < jobs.size(); ++j) {
             const GemmJob& o = jobs[j];
-            if (done[j] || o.M != g.M || o.N != g.N || o.K != g.K || o.lda != g.lda || o.ldb != g.ldb || o.ta != g.ta ||
-                o.tb != g.tb || o.sym != g.sym || o.alpha != g.alpha || o.tri != g.tri)
+            if (done[j] || !same_shape(o, g))
                 continue;
             done[j] = true;
             A.push_back(o.A);
@@ -371,9 +396,42 @@ void gemm_grouped(xrs_handle_t h, const std::vector<GemmJob>& jobs) {
     }
 }
 
-struct ChainStatus {
-    int* status = nullptr;    // pinned host copy of the factorisation statuses
+// Lanes of a chain pass of an unsharded TT: what leaves the main lane for side stream 0, so
+// that between the batched Cholesky and k_dev_identity_many the main lane holds batched launches only.
+constexpr int kLaneInverses = 1;     // stage 1: the explicit inverses Z_k
+constexpr int kLaneTransforms = 2;   // stage 2: the transforms outside the largest same-shape group
+constexpr int kLaneGrams = 4;        // stage 3: their Grams in the check (only with stage 2)
+constexpr int kRoundLanes = kLaneInverses | kLaneTransforms | kLaneGrams;
+// The side lane pays one event hop (18-20 us) to start behind the factorisations and the main lane's wait for
+// Z needs hop + inverses (25-40 us) + hop, 60-80 us in all, to be hidden by the batched right factors. That
+// launch runs 4.0 GFLOP (dense count, bench shape: 6 x 5120 x 256 x 256) in 76-92 us, so below about 3 GFLOP
+// the waits are exposed and the pass keeps to one lane: at rank 128 (0.5 GFLOP, batched launches of 10-17 us)
+// the lanes measured 0.4875 against 0.450 ms per round. (Only the two ends are measured, profiles/r07.)
+constexpr double kLaneMinFlops = 3e9;
+// XRS_ROUND_LANES=<mask 0..7> (diagnostics and tests: the stages' A/B runs, the lanes at small shapes) takes
+// the place of both the default and the size rule; read at every pass.
+static int round_lanes(double main_right_flops) {
+    const char* e = std::getenv("XRS_ROUND_LANES");
+    if (e && e[0] >= '0' && e[0] <= '7' && e[1] == 0) return e[0] - '0';
+    return main_right_flops >= kLaneMinFlops ? kRoundLanes : 0;
+}
+
+// A chain pass in flight, from chain_pass to the end of its chain_check. The pass's temporaries are read on
+// both lanes, so they go back to the (main lane's) pool only after the side lane has been joined into the
+// main stream: `aux` is the last member, destroyed -- and so joined -- first, on a throw as well.
+struct ChainPass {
+    int* status = nullptr;    // pinned host copy of the factorisation statuses (valid after chain_check)
     int count = 0;
+    DevBuf dev_status;
+    std::vector<DevBuf> temps;        // L_k, Z_k, W_k and the Cholesky front end's own
+    std::vector<bool> on_main;        // core k of the result was written on the main lane
+    int lanes = 0;
+    std::unique_ptr<StreamFork> aux;  // open from behind the factorisations to the check's join
+    void finish() {   // after the join: everything back to the pool
+        aux.reset();
+        temps.clear();
+        dev_status.reset();
+    }
 };
 
 // One chain orthogonalisation pass over the current cores: the right Gram chain H_k (and, with
@@ -382,76 +440,131 @@ struct ChainStatus {
 // only) -- then every core is transformed independently: C_k = L_k^{-1} M_k (I (x) L_{k+1}),
 // C_0 = M_0 (I (x) L_1). In exact arithmetic the C_k (k >= 1) have orthonormal rows and represent the
 // same tensor. Nothing is synchronised: the factorisation statuses are copied to pinned host memory
-// behind the transforms and judged by chain_check (a failed factorisation only makes C garbage, which
-// is then discarded). The new cores C are candidates owned by `sw`; the pass's own temporaries go back to
-// the pool when it returns (stream-ordered: the check's buffers reuse them).
-ChainStatus chain_pass(Sweep& sw, TT& t, bool certify, std::vector<double*>& C) {
+// behind the check's Grams and judged after chain_check (a failed factorisation only makes C garbage,
+// which is then discarded). The new cores C are candidates owned by `sw`; the pass's own temporaries stay
+// with the returned ChainPass until chain_check has joined the lanes.
+//
+// Lanes (unsharded; a sharded TT keeps everything on the handle's stream, where its all-reduces go):
+//   main : chains' join -> batched Cholesky -> [fork] -> right factors, largest group -> [wait mark]
+//          -> left factors, largest group -> (chain_check) Grams, largest group -> [join] -> deviations, D2H
+//   aux  : [fork] -> explicit inverses Z_k -> [mark] -> right, then left factors of the other groups
+//          -> (chain_check) their Grams -> [join]
+// The batched right factors need only L, so the inverses (25-40 us on a few CUs) run beside them. The small
+// groups are the boundary cores: a handful of workgroups each, which on the main lane cost their full latency
+// in front of the next batched launch. Every buffer is allocated before the fork, on the main lane's pool.
+ChainPass chain_pass(Sweep& sw, TT& t, bool certify, std::vector<double*>& C) {
     const size_t d = t.d;
     xrs_handle_t h = t.h;
     std::vector<double*> G, H;
-    std::vector<DevBuf> gram_store, Lf(d);
+    std::vector<DevBuf> gram_store;   // read by the factorisations only (main lane): released on return
+    ChainPass p;                      // (after gram_store: on a throw its fork restores the main pool first)
     XRS_MARK("pass");
     gram_chains(t, G, H, gram_store, certify);
     open_dot_gate(h);   // a gated async <x,y> runs beside the factorisations and transforms below
     XRS_MARK("chains");
     // every factorisation of the pass through one front-end call (chol_batch.hpp): per edge H_k = L_k L_k^T with
     // Z_k = L_k^{-1}, and with `certify` the status-only certificates of G_k and H_k
-    std::vector<DevBuf> Z(d), Cs;
-    for (size_t k = 1; k < d; ++k) Z[k] = DevBuf(h, t.r[k] * t.r[k] * 8);
+    std::vector<double*> Lf(d, nullptr), Z(d, nullptr), W(d, nullptr);
+    auto temp = [&](size_t elems) {
+        p.temps.emplace_back(h, elems * 8);
+        return p.temps.back().d();
+    };
     std::vector<CholJob> jobs;
     for (size_t k = 1; k < d; ++k) {
         const size_t a = t.r[k];
-        Lf[k] = DevBuf(h, a * a * 8);
-        jobs.push_back({H[k], int(a), Lf[k].d(), Z[k].d()});
+        Z[k] = temp(a * a);
+        Lf[k] = temp(a * a);
+        jobs.push_back({H[k], int(a), Lf[k], Z[k]});
         if (certify) {
             jobs.push_back(CholJob::certificate(G[k], int(a), kGramShift));
             jobs.push_back(CholJob::certificate(H[k], int(a), kGramShift));
         }
     }
-    const int cnt = chol_status_count(jobs);
-    int* host_status = scratch::host<int>(h, scratch::kHostChainStatus, size_t(cnt));
-    DevBuf st(h, size_t(cnt) * 4 + 64);
-    chol_enqueue(h, jobs, st.as<int>(), Cs);
-    XRS_HIP(hipMemcpyAsync(host_status, st.d(), size_t(cnt) * 4, hipMemcpyDeviceToHost, h->stream));
-    XRS_MARK("potrf");
-    // The d transforms are independent: same-shape GEMMs go out as one batched launch each, all on the
-    // main stream (cross-stream event hops cost ~20 us each here; a batch fills the chip as well as
-    // concurrent streams do). The left factor is applied as a GEMM with the explicit inverse
-    // Z_k = L_k^{-1} (one batched launch); the check below certifies the result either way.
+    p.count = chol_status_count(jobs);
+    p.status = scratch::host<int>(h, scratch::kHostChainStatus, size_t(p.count));
+    p.dev_status = DevBuf(h, size_t(p.count) * 4 + 64);
     C.assign(d, nullptr);
-    std::vector<DevBuf> W(d);
     for (size_t k = 0; k < d; ++k) {
         C[k] = sw.core(t.size(k));
-        if (k > 0 && k + 1 < d) W[k] = DevBuf(h, t.size(k) * 8);
+        if (k > 0 && k + 1 < d) W[k] = temp(t.size(k));
     }
-    // L_k and Z_k of the register-resident kernels (r <= 256) hold exact zeros above the diagonal: their
-    // zero K-blocks are skipped (5/8 of the work at r = 256)
+    CholInverses inverses;
+    chol_enqueue_factors(h, jobs, p.dev_status.as<int>(), p.temps, inverses);
+    XRS_MARK("potrf");
+    // The d transforms are independent: same-shape GEMMs go out as one batched launch each. The left
+    // factor is applied as a GEMM with the explicit inverse Z_k = L_k^{-1}; the check certifies the result
+    // either way. L_k and Z_k of the register-resident kernels (r <= 256) hold exact zeros above the
+    // diagonal: their zero K-blocks are skipped (5/8 of the work at r = 256)
     std::vector<GemmJob> right, left;
     for (size_t k = 0; k + 1 < d; ++k) {   // right factors: M_k (I (x) L_{k+1}), (r_k n_k) x r_{k+1} x r_{k+1}
         const size_t b = t.r[k + 1];
-        right.push_back({t.rows_left(k), b, b, b, b, false, false, t.core[k], Lf[k + 1].d(), k == 0 ? C[k] : W[k].d()});
+        right.push_back({t.rows_left(k), b, b, b, b, false, false, t.core[k], Lf[k + 1], k == 0 ? C[k] : W[k]});
         right.back().tri = b <= 256 ? kTriB : 0;
     }
     for (size_t k = 1; k < d; ++k) {       // left factors: Z_k (r_k x r_k) times the r_k x (n_k r_{k+1}) unfolding
         const size_t a = t.r[k], cols = t.cols_right(k);
-        left.push_back({a, cols, a, a, cols, false, false, Z[k].d(), k + 1 < d ? W[k].d() : t.core[k], C[k]});
+        left.push_back({a, cols, a, a, cols, false, false, Z[k], k + 1 < d ? W[k] : t.core[k], C[k]});
         left.back().tri = a <= 256 ? kTriA : 0;
     }
-    gemm_grouped(h, right);
-    gemm_grouped(h, left);
+    // right job i is core i, left job i is core i + 1; the left factor of an inner core reads W_k, its right
+    // factor's output, so the two lanes are self-contained only if both groupings keep the same inner cores
+    // on the main lane. (They do whenever the inner cores share one shape. Otherwise -- all shapes
+    // different, d = 3 -- the transforms stay on the main lane: correct, no faster.)
+    std::vector<bool> rmain = largest_group(right), lmain = largest_group(left);
+    double main_right_flops = 0.0;
+    for (size_t i = 0; i < right.size(); ++i)
+        if (rmain[i]) main_right_flops += 2.0 * double(right[i].M) * double(right[i].N) * double(right[i].K);
+    p.lanes = t.sharded() ? 0 : round_lanes(main_right_flops);
+    bool closed = true;
+    for (size_t k = 1; k + 1 < d; ++k) closed = closed && rmain[k] == lmain[k - 1];
+    if (!closed || !(p.lanes & kLaneTransforms)) {
+        p.lanes &= kLaneInverses;
+        rmain.assign(right.size(), true);
+        lmain.assign(left.size(), true);
+    }
+    const bool inv_aux = (p.lanes & kLaneInverses) != 0;
+    if (!inv_aux) chol_enqueue_inverses(h, inverses);
+    if (p.lanes) p.aux = std::make_unique<StreamFork>(h);   // the side lane starts behind the factorisations
+    StreamFork* aux = p.aux.get();
+    if (inv_aux) {
+        aux->side();
+        chol_enqueue_inverses(h, inverses);
+        aux->mark_side();
+        aux->main();
+    }
+    auto part = [](const std::vector<GemmJob>& jobs_, const std::vector<bool>& on_main, bool want) {
+        std::vector<GemmJob> out;
+        for (size_t i = 0; i < jobs_.size(); ++i)
+            if (on_main[i] == want) out.push_back(jobs_[i]);
+        return out;
+    };
+    gemm_grouped(h, part(right, rmain, true));
+    if (aux) {
+        aux->side();
+        gemm_grouped(h, part(right, rmain, false));
+        gemm_grouped(h, part(left, lmain, false));
+        aux->main();
+        // Z: recorded behind the inverses, long fired when the batched right factors end
+        if (inv_aux) aux->main_wait_mark();
+    }
+    gemm_grouped(h, part(left, lmain, true));
+    p.on_main.assign(d, true);
+    p.on_main[0] = rmain[0];
+    for (size_t k = 1; k < d; ++k) p.on_main[k] = lmain[k - 1];
     XRS_MARK("transforms");
-    return {host_status, cnt};
+    return p;
 }
 
 // True when every factorisation of the pass succeeded (valid after the stream has been synchronised).
-bool chain_status_ok(const ChainStatus& p) {
+bool chain_status_ok(const ChainPass& p) {
     static const bool dbg = std::getenv("XRS_DEBUG_ROUND") != nullptr;
     const int i = first_bad(p.status, p.count);
     if (i >= 0 && dbg) std::fprintf(stderr, "chain_pass: status word %d of %d is %d (a factorisation failed)\n", i, p.count, p.status[i]);
     return i < 0;
 }
 
-int orth_enqueue(TT& t, std::vector<DevBuf>& keep, const std::vector<double*>& C, const size_t* r, bool rows, double* host) {
+int orth_enqueue(TT& t, std::vector<DevBuf>& keep, const std::vector<double*>& C, const size_t* r, bool rows, double* host,
+                 StreamFork* aux, const std::vector<bool>* on_main) {
     xrs_handle_t h = t.h;
     const size_t first = rows ? 1 : 0, cnt = t.d - 1;
     size_t total = 0;
@@ -471,7 +584,34 @@ int orth_enqueue(TT& t, std::vector<DevBuf>& keep, const std::vector<double*>& C
         da.G[i] = G;
         da.n[i] = int(g);
     }
-    gemm_grouped(h, grams);
+    // Two lanes: a Gram may only run on the lane that wrote its core (the other lane's writer is not ordered
+    // before it), so the split holds only if the largest group is exactly the main lane's cores; the Grams'
+    // shapes and flops are the left factors', so it does whenever chain_pass split its transforms. Otherwise
+    // the lanes are joined first and every Gram runs on the main lane.
+    std::vector<bool> gmain;
+    if (aux && on_main && !t.sharded()) {
+        gmain = largest_group(grams);
+        bool agree = true;
+        for (size_t i = 0; i < cnt; ++i) agree = agree && gmain[i] == (*on_main)[first + i];
+        if (!agree) gmain.clear();
+    }
+    if (!gmain.empty()) {
+        std::vector<GemmJob> mine, others;
+        for (size_t i = 0; i < cnt; ++i) (gmain[i] ? mine : others).push_back(grams[i]);
+        gemm_grouped(h, mine);
+        aux->side();
+        try {
+            gemm_grouped(h, others);
+        } catch (...) {   // the caller's `keep` is released before the fork's owner unwinds: main pool first
+            aux->main();
+            throw;
+        }
+        aux->main();
+        aux->join();
+    } else {
+        if (aux) aux->join();
+        gemm_grouped(h, grams);
+    }
     t.reduce(all, total);   // sharded: complete the mode sums across ranks (no-op otherwise)
     da.out = all + total;
     hipLaunchKernelGGL(k_dev_identity_many, dim3(unsigned(cnt), kOrthSlices), dim3(256), 0, h->stream, da);
@@ -480,16 +620,22 @@ int orth_enqueue(TT& t, std::vector<DevBuf>& keep, const std::vector<double*>& C
     return int(cnt) * kOrthSlices;
 }
 
-// max_k max |C_k C_k^T - I| over cores 1..d-1 (mode sums completed across ranks when sharded).
-// Synchronises the stream (so the pass statuses are readable afterwards).
-double chain_check(TT& t, const std::vector<double*>& C) {
+// max_k max |C_k C_k^T - I| over cores 1..d-1 (mode sums completed across ranks when sharded) of the pass `p`
+// that produced C. Joins the pass's lanes, copies its factorisation statuses behind the deviations and
+// synchronises the stream: the statuses are readable afterwards, and the pass's temporaries are back in the pool.
+double chain_check(TT& t, const std::vector<double*>& C, ChainPass& p) {
     XRS_MARK("check");
+    xrs_handle_t h = t.h;
     std::vector<DevBuf> keep;
-    double* hd = scratch::host<double>(t.h, scratch::kHostChainDev, (t.d - 1) * kOrthSlices);
-    const int nchk = orth_enqueue(t, keep, C, t.r, true, hd);
+    double* hd = scratch::host<double>(h, scratch::kHostChainDev, (t.d - 1) * kOrthSlices);
+    const bool split = p.aux && (p.lanes & kLaneGrams);
+    if (p.aux && !split) p.aux->join();   // the Grams read cores that the side lane wrote
+    const int nchk = orth_enqueue(t, keep, C, t.r, true, hd, split ? p.aux.get() : nullptr, &p.on_main);
+    XRS_HIP(hipMemcpyAsync(p.status, p.dev_status.d(), size_t(p.count) * 4, hipMemcpyDeviceToHost, h->stream));
     XRS_MARK("enq");
-    host_wait(t.h);
+    host_wait(h);
     XRS_MARK("sync");
+    p.finish();
     return worst_dev(hd, nchk);
 }
 
@@ -510,16 +656,16 @@ bool round_chain(TT& t, const size_t* max_ranks, double eps) {
     HostMarks marks;
     Sweep sw(t);
     std::vector<double*> C;
-    const ChainStatus p1 = chain_pass(sw, t, true, C);
-    double dev = chain_check(t, C);
+    ChainPass p1 = chain_pass(sw, t, true, C);
+    double dev = chain_check(t, C, p1);
     if (!chain_status_ok(p1)) return false;
     if (!(dev <= kOrthTol)) {
         if (dbg) std::fprintf(stderr, "round_chain: pass 1 orthogonality %.3e, second pass\n", dev);
         TT t2 = t;
         t2.core = C.data();
         std::vector<double*> C2;
-        const ChainStatus p2 = chain_pass(sw, t2, false, C2);
-        const double dev2 = chain_check(t2, C2);
+        ChainPass p2 = chain_pass(sw, t2, false, C2);
+        const double dev2 = chain_check(t2, C2, p2);
         const bool ok2 = chain_status_ok(p2);
         if (dbg) std::fprintf(stderr, "round_chain: pass 2 orthogonality %.3e (factors %s)\n", dev2, ok2 ? "ok" : "failed");
         const bool take2 = ok2 && dev2 <= kOrthTol;
@@ -542,8 +688,8 @@ bool round_chain(TT& t, const size_t* max_ranks, double eps) {
 bool reorthonormalize(TT& t) {
     Sweep sw(t);
     std::vector<double*> C;
-    const ChainStatus p = chain_pass(sw, t, false, C);
-    const double dev = chain_check(t, C);
+    ChainPass p = chain_pass(sw, t, false, C);
+    const double dev = chain_check(t, C, p);
     if (!(chain_status_ok(p) && dev <= kOrthTol)) return false;
     sw.commit(C);
     return true;

@@ -158,8 +158,13 @@ __global__ void k_dev_identity_many(const DevIdArgs args);
 // cores 1..d-1 (`rows`) or max |C_k^T C_k - I| of the left unfoldings of cores 0..d-2, kOrthSlices values per
 // core. Enqueues the Grams (one buffer, pushed onto `keep`; sharded: completed by ONE all-reduce), the
 // deviations and their copy to the pinned `host`; returns the number of values, valid after the next host wait.
+// With `aux` (an open fork of an unsharded TT; `on_main[k]`: core k was written on the main lane) only the
+// same-shape group of Grams with the most flops stays on the main lane; the others go to the fork's side lane
+// behind the cores' writers there, and the fork is joined before the deviations. Either way the fork is joined
+// when the call returns.
 constexpr int kOrthSlices = 16;
-int orth_enqueue(TT& t, std::vector<DevBuf>& keep, const std::vector<double*>& C, const size_t* r, bool rows, double* host);
+int orth_enqueue(TT& t, std::vector<DevBuf>& keep, const std::vector<double*>& C, const size_t* r, bool rows, double* host,
+                 StreamFork* aux = nullptr, const std::vector<bool>* on_main = nullptr);
 // NaN-propagating maximum of the check's values
 inline double worst_dev(const double* v, int count) {
     double worst = 0.0;
@@ -185,6 +190,9 @@ struct GemmJob {
     int tri = 0;        // triangular operands (kTriA / kTriB, gemm): zero K-blocks skipped
 };
 void gemm_grouped(xrs_handle_t h, const std::vector<GemmJob>& jobs);
+// in_largest[i]: job i belongs to the same-shape group (gemm_grouped's grouping) with the most flops, the
+// first such group on a tie. That group fills the chip; the others are a handful of workgroups each.
+std::vector<bool> largest_group(const std::vector<GemmJob>& jobs);
 
 // largest rank of the certified chain / truncating rounds (blocked Cholesky above 512, the 1024-column
 // register tiling of the block Jacobi SVD)
