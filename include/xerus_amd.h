@@ -187,8 +187,14 @@ int xrs_sym_tridiag(xrs_handle_t handle, double* d, double* e, const double* A, 
  *  1 <= kk <= n): the certified truncating round's replacement of the per-edge SVD when the edge Gram is
  *  certified well conditioned (no reference counterpart: the reference always runs dgesdd, tensor.cpp:1424-1489).
  *  Householder tridiagonalisation, multisection + inverse iteration, back-transformation. lam: kk descending;
- *  Ut: kk x n, row i = the eigenvector of lam[i]. *status (host): 0, or -1 when a multisection did not
- *  converge. Synchronises. */
+ *  Ut: kk x n, row i = the eigenvector of lam[i]. Eigenvalues closer than 1e-3 ||A|| form a cluster, of any size up
+ *  to kk; its vectors are orthonormalised among themselves, so with *status == 0 the rows of Ut are orthonormal
+ *  and each spans its eigenvalue's invariant subspace to working accuracy whatever the multiplicities (scalar,
+ *  rank-deficient and block-diagonal matrices included). *status (host): 0; -1 when a multisection did not
+ *  converge; -3 when a vector of a cluster came out numerically dependent on the cluster's earlier ones (it kept
+ *  less than 1e-4 of its norm against them). On a negative status lam is valid for -3 only and Ut must not be
+ *  used: compute the vectors another way (the rounds fall back to their Jacobi / reference routes). Deterministic:
+ *  the same input gives the same bits. Synchronises. */
 int xrs_sym_eig_top(xrs_handle_t handle, double* lam, double* Ut, int* status, const double* A, size_t n, size_t kk);
 
 /* ---------------------------------------------------------------- TT hot path (ttNetwork.cpp) */

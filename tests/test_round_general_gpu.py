@@ -156,3 +156,41 @@ def test_tall_right_end_after_cut(handle, ref, max_rank, eps):
     z = ref.tt_add(x, y)
     assert z.ranks == [6, 10, 10, 10, 6]
     _check(handle, ref, z, [max_rank] * 5, eps, ("general",) if eps > EPSILON else ("general", "truncate"))
+
+
+def test_edge_cluster_of_20(handle, ref):
+    """Every edge Gram with one eigenvalue of exact multiplicity 20 and a distinct tail: 28 mutually orthogonal
+    rank-one terms of order 4 and mode size 28, weights 1 (20 times) and 8 distinct ones in (0.1, 0.6) with gaps
+    0.06, every mode rotated by a seeded orthogonal matrix and a seeded orthogonal gauge pair inserted on every
+    edge (dense Grams). round(24) cuts in the distinct tail, so the answer is unique: the four smallest terms go
+    and the error is the root of their squared weights. The cluster's 20 eigenvectors must come back orthonormal
+    from the eigensolver (or the round must notice and fall back): oracle ranks and error, right-orthonormal
+    cores to 1e-10, whichever path runs."""
+    from syev_spectra import haar
+    from ttutil import tt_diff_norm
+
+    n = 28
+    w = np.concatenate([np.ones(20), 0.58 - 0.06 * np.arange(8)])
+    Q = [haar(n, 151 + k) for k in range(4)]
+    G = [haar(n, 161 + k) for k in range(3)]
+    cores = []
+    for k in range(4):
+        C = np.zeros((n, n, n))   # (left rank, mode, right rank): term j couples only to itself
+        C[np.arange(n), :, np.arange(n)] = Q[k].T
+        if k == 0:
+            C = np.einsum("j,jia->ia", w, C)[None]
+        elif k == 3:
+            C = C.sum(axis=2)[:, :, None]
+        if k > 0:
+            C = np.einsum("ja,jib->aib", G[k - 1], C)
+        if k < 3:
+            C = np.einsum("aij,jb->aib", C, G[k])
+        cores.append(np.ascontiguousarray(C))
+    x = ref.TT(cores)
+    assert x.ranks == [n] * 3
+    g, _, path = _check(handle, ref, x, [24] * 3, EPSILON, ("truncate", "general", "reference"))
+    print(f"edge cluster of 20: path {path}")
+    err, nrm = tt_diff_norm(g.cores(), x.cores)
+    want = np.sqrt(np.sum(w[-4:] ** 2))
+    assert abs(nrm - np.linalg.norm(w)) <= 1e-12 * nrm
+    assert abs(err - want) <= 1e-10 * want

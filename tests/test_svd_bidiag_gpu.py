@@ -12,6 +12,8 @@ import sys
 import numpy as np
 import pytest
 
+import syev_spectra
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -59,7 +61,7 @@ def test_svd_bidiag_strict():
         assert r["se"] <= 1e-12 and r["mono"], r
 
 
-@pytest.mark.parametrize("kind", ["rank_deficient", "identity", "zero", "twin", "graded12"])
+@pytest.mark.parametrize("kind", ["rank_deficient", "identity", "zero", "twin", "graded12", "cluster20", "cluster24", "cluster25"])
 def test_svd_square_fallback_cases(handle, ref, kind):
     """Spectra the bidiagonal path may hand to the Jacobi fallback: the default mode still meets dgesdd's bars."""
     n = 96
@@ -73,7 +75,11 @@ def test_svd_square_fallback_cases(handle, ref, kind):
     else:
         U, _ = np.linalg.qr(rng.standard_normal((n, n)))
         V, _ = np.linalg.qr(rng.standard_normal((n, n)))
-        s = np.repeat(np.linspace(1, 2, n // 2), 2) if kind == "twin" else np.logspace(0, -12, n)
+        if kind.startswith("cluster"):   # one singular value of that exact multiplicity (on both sides of the cluster
+            # pass's limit of 24 vectors), the others distinct with gaps > 1e-2 ||A||
+            s = syev_spectra.cluster_spectrum(n, int(kind[7:]), 5, 0.0, 0.1025) / 10.0
+        else:
+            s = np.repeat(np.linspace(1, 2, n // 2), 2) if kind == "twin" else np.logspace(0, -12, n)
         A = (U * s) @ V.T
     Uh, Sh, Vh = (x.numpy() for x in handle.svd(handle.array(A)))
     Sr = ref.svd(A)[1]

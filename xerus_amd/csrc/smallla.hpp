@@ -71,8 +71,9 @@ void jacobi_usv(xrs_handle_t h, const double* W, int ldw, bool trans, int p, int
 // Eigenpairs of the kk largest eigenvalues of a symmetric n x n matrix A (lower triangle read, 2 <= n <= 256):
 // Householder tridiagonalisation (one workgroup, register-resident), multisection + inverse iteration per
 // eigenvalue, back-transformation (syev.hip). lam (kk, optional) descending, S = sqrt(max(lam, 0))
-// (optional), Ut rows = the eigenvectors (kk x n, row stride ldu). *status_dev set to -1 if a
-// multisection did not converge (left untouched otherwise). Enqueued only.
+// (optional), Ut rows = the eigenvectors (kk x n, row stride ldu). *status_dev (never null) set to -1 if a
+// multisection did not converge and to -3 if a vector of a cluster collapsed in its Gram-Schmidt pass (left
+// untouched otherwise): the vectors are not to be used on a negative status. Enqueued only.
 bool sym_eig_top_fits(int n, int kk);   // the truncating round's policy (n <= 256 unless XRS_SYEV_MAX lowers it)
 void sym_eig_top(xrs_handle_t h, const double* A, int lda, int n, int kk, double* lam, double* S, double* Ut, int ldu, int* status_dev);
 // Householder tridiagonalisation (syev.hip's k_sytrd): d (n), e (n - 1) of T = Q^T A Q

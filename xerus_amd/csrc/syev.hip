@@ -12,7 +12,8 @@
 //   2. k_stebz_stein: one wave per wanted eigenvalue (kk workgroups in parallel): Sturm-count
 //      multisection on 64 points per round (~9 rounds to full precision; the counts as sign changes of the
 //      three-term minor recurrence, one FMA per level on the chain), then inverse iteration with the
-//      partially pivoted LU of T - lambda I (dgttrf / dgttrs), three solves from a fixed start vector, every
+//      partially pivoted LU of T - (lambda + 64 u ||T||) I (dgttrf / dgttrs), three solves from a start vector
+//      hashed from (row, eigenvalue index) (stein_start; the shift's offset keeps clusters independent), every
 //      chain fed by operands read ahead in blocks (r04: 104 -> 73 us at order 128, the chains now
 //      FP64-issue-bound, profiles/r04/stein_phases_r04z.txt).
 //      Measured alternatives (profiles/r03/stein_variants_r03r.txt): a single twisted-factorisation solve
@@ -21,7 +22,8 @@
 //   3. k_ormtr: the eigenvectors back to A's coordinates, u = H_0 ... H_{n-2} z, one wave per vector
 //      (64 lanes, 4 vectors per workgroup), the reflectors staged through LDS in chunks.
 //   2b. k_cluster_orth: vectors of eigenvalue clusters (gaps <= 1e-3 ||T||, dstein's ORTOL) orthonormalised
-//      by two modified Gram-Schmidt passes (dstein's reorthogonalisation within a cluster).
+//      by two modified Gram-Schmidt passes (dstein's reorthogonalisation within a cluster); a vector that
+//      collapses against its predecessors sets status -3 (never a wrong vector with status 0).
 // Measured dead end (round 4, profiles/r04/twostage_*_r04h.*): a two-stage tridiagonalisation (dense -> band
 // 16 by MFMA panel updates, band -> tridiagonal by bulge chasing, Q2/Q1 back-transformation) ran 303 + 333
 // + 186 us at n = 128 against this kernel's 330 us (cfg3 round(64): 8.25 vs 4.5 ms): in one workgroup every
@@ -502,6 +504,24 @@ __global__ void __launch_bounds__(512) k_sytrd_l512(const double* __restrict__ A
         }
 }
 
+// Entry i of the inverse iteration's start vector for eigenvalue q: uniform in (-1, 1) (dstein's dlarnv
+// distribution), never 0, from a bijective 32-bit mix (murmur3's finaliser) of (i, q) -- no two of the SY_MAX^2
+// entries share their bits' source, so the vectors of a cluster start independent in every coordinate subset.
+// (The first formula was 1 + ((37 i + 11 q) mod 17) / 17, of period 17 in i and in q: the members q and q + 17
+// of a cluster started identically and the 17 distinct vectors agreed on coordinates i = i' (mod 17): clusters of
+// 18 and more, c I of order >= 18 and diagonals with repeated entries came back with zero or noise rows and
+// status 0, tests/test_syev_gpu.py::test_sym_eig_top_spectra.) Formed once per entry by the whole workgroup, off
+// the chains.
+__device__ __forceinline__ double stein_start(int i, int q) {
+    unsigned h = unsigned(i) | (unsigned(q) << 16);
+    h ^= h >> 16;
+    h *= 0x85ebca6bu;
+    h ^= h >> 13;
+    h *= 0xc2b2ae35u;
+    h ^= h >> 16;
+    return (double(h >> 8) + 0.5) * (1.0 / 8388608.0) - 1.0;
+}
+
 // one 64-lane workgroup per wanted eigenvalue: block q -> the q-th largest (ascending index n - 1 - q).
 // Zt (kk x ldz): row q = the eigenvector of T (normalised); lam[q]. status[0] <- -1 if a multisection
 // did not reach full precision.
@@ -625,7 +645,16 @@ __global__ void __launch_bounds__(64 * SW_WAVES) k_stebz_stein(const double* __r
         // larger), tiny pivots replaced by u ||T|| (dlagtf's perturbation). The running diagonal and
         // superdiagonal entries are carried in registers (no LDS store -> load per level on the dependent
         // chain); the original entries of the next row are independent of it.
-        double dcur = sd[0] - lmb, ucur = n > 1 ? se[0] : 0.0;
+        // The shift is moved off the eigenvalue by 64 u ||T||: the members of a (nearly) multiple eigenvalue get
+        // (nearly) the same shift, and the copies of that eigenvalue in T lie a few u ||T|| apart; a shift within
+        // 0.01 u ||T|| of one of them weights its vector 1e6 times above the others after three solves, every
+        // member comes back as that one vector and k_cluster_orth normalises what is left of it (measured: exact
+        // multiplicities 18..64 at 1e-12..1e-10 in orthogonality and residual). 64 u ||T|| away the copies are
+        // weighted within a small factor of each other and the members stay as independent as their start
+        // vectors. Separated eigenvalues (gap > 1e-3 ||T||) still converge in one solve, (64 u ||T|| / gap) per
+        // solve; for members ~64 u ||T|| apart the residual is bounded by the shift's distance, 1.4e-14 ||T||.
+        const double lms = lmb + 64.0 * 2.2204460492503131e-16 * fmax(amax, 1e-300);
+        double dcur = sd[0] - lms, ucur = n > 1 ? se[0] : 0.0;
         auto lu_level = [&](int i, double l, double dn, double un) {
             if (fabs(dcur) >= fabs(l)) {
                 const double f = dcur != 0.0 ? l * rcpn<NEWTON>(dcur) : 0.0;
@@ -653,13 +682,13 @@ __global__ void __launch_bounds__(64 * SW_WAVES) k_stebz_stein(const double* __r
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 l8[u] = se[i + u];
-                d8[u] = sd[i + u + 1] - lmb;
+                d8[u] = sd[i + u + 1] - lms;
                 u8[u] = se[i + u + 1];
             }
 #pragma unroll
             for (int u = 0; u < 8; ++u) lu_level(i + u, l8[u], d8[u], u8[u]);
         }
-        for (; i + 1 < n; ++i) lu_level(i, se[i], sd[i + 1] - lmb, i + 2 < n ? se[i + 1] : 0.0);
+        for (; i + 1 < n; ++i) lu_level(i, se[i], sd[i + 1] - lms, i + 2 < n ? se[i + 1] : 0.0);
         ld[n - 1] = dcur;
         ldl[n - 1] = 0.0;
         ldu[n - 1] = 0.0;
@@ -674,7 +703,7 @@ __global__ void __launch_bounds__(64 * SW_WAVES) k_stebz_stein(const double* __r
             double p = ld[i];
             if (fabs(p) < tiny) p = copysign(tiny, p == 0.0 ? 1.0 : p);
             ild[i] = rcp2(p);
-            lb[i] = 1.0 + double((i * 37 + q * 11) % 17) * (1.0 / 17.0);
+            lb[i] = stein_start(i, q);
         }
     }
     __syncthreads();
@@ -838,7 +867,13 @@ __global__ void __launch_bounds__(256) k_ormtr(const double* __restrict__ V, con
 // dstein reorthogonalises against the earlier vectors of a cluster). One workgroup; without clusters it only
 // scans the eigenvalues.
 // maxc: clusters larger than this are left alone and *status set to -2 (the bidiagonal SVD's fallback signal: its
-// Jacobi route is cheaper than a long Gram-Schmidt chain); status may be null when maxc >= kk.
+// Jacobi route is cheaper than a long Gram-Schmidt chain).
+// A vector that keeps less than kClusterCollapse of its unit norm after the first pass was numerically dependent on
+// its predecessors: normalising the remainder multiplies inverse iteration's error outside the cluster's invariant
+// subspace (up to u ||T|| / ortol = 1.1e-13) by more than 1e4, so the vector is not trusted and *status set to -3
+// (the round and the bidiagonal SVD fall back on any negative status). Independent start vectors leave about
+// 1 / sqrt(members) or more.
+constexpr double kClusterCollapse = 1e-4;
 __global__ void __launch_bounds__(256) k_cluster_orth(const double* __restrict__ lam, const double* __restrict__ d,
                                                       const double* __restrict__ e, int n, int kk, double* __restrict__ Zt, int ldz,
                                                       int maxc, int* __restrict__ status) {
@@ -882,6 +917,7 @@ __global__ void __launch_bounds__(256) k_cluster_orth(const double* __restrict__
                     __syncthreads();
                 }
                 const double nn = sqrt(dot(zj, zj));
+                if (pass == 0 && !(nn >= kClusterCollapse) && tid == 0) status[0] = -3;
                 const double inv = nn > 0.0 ? 1.0 / nn : 0.0;
                 for (int k = tid; k < n; k += 256) zj[k] *= inv;
                 __syncthreads();
@@ -1310,7 +1346,7 @@ XRS_REQUIRE(n >= 2 && n <= SY_MAX && kk >= 1 && kk <= n, "sym_eig_top: need 2 <=
     hipLaunchKernelGGL(k_stebz_stein<2>, dim3(kk), dim3(64 * SW_WAVES), 0, h->stream, dbuf.d(), ebuf.d(), n, lm, Ut, ldu, status,
                        stp ? stp + 768 : nullptr);
     check_launch("k_stebz_stein");
-    hipLaunchKernelGGL(k_cluster_orth, dim3(1), dim3(256), 0, h->stream, lm, dbuf.d(), ebuf.d(), n, kk, Ut, ldu, kk, nullptr);
+    hipLaunchKernelGGL(k_cluster_orth, dim3(1), dim3(256), 0, h->stream, lm, dbuf.d(), ebuf.d(), n, kk, Ut, ldu, kk, status);
     check_launch("k_cluster_orth");
     // (a blocked form -- 16 reflectors' dots together, their recurrence through the block's reflector Gram --
     // measured slower: 162 vs 108 us at order 256, 55 vs 38 us at 128, plus 22-28 us for the Grams; r04ah)
