@@ -8,6 +8,7 @@
 //     output entry, a strided partial sum per thread and a fixed-order LDS tree, so results do not depend
 //     on scheduling.
 #include "adf.hpp"
+#include "reduce_dev.hpp"
 
 namespace xrs {
 namespace adf {
@@ -65,21 +66,6 @@ __global__ void __launch_bounds__(kThreads) k_evaluate(size_t M, const double* _
     }
 }
 
-// fixed-order sum of the block's partial values (every thread returns the total)
-__device__ double block_sum(double v) {
-    __shared__ double red[kThreads];
-    red[threadIdx.x] = v;
-    __syncthreads();
-#pragma unroll
-    for (int o = kThreads / 2; o > 0; o >>= 1) {
-        if (int(threadIdx.x) < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    const double t = red[0];
-    __syncthreads();
-    return t;
-}
-
 // one workgroup per entry (i, t, j) of D (a x n x b)
 __global__ void __launch_bounds__(kThreads) k_projected_gradient(size_t M, const double* __restrict__ F, const double* __restrict__ B,
                                                                  const double* __restrict__ res, const double* __restrict__ vec,
@@ -95,7 +81,7 @@ __global__ void __launch_bounds__(kThreads) k_projected_gradient(size_t M, const
     } else {      // rank one: every measurement, weighted by its vector entry t
         for (size_t m = threadIdx.x; m < M; m += kThreads) s = fma(res[m] * vec[m * n + t] * F[m * a + i], B[m * b + j], s);
     }
-    s = block_sum(s);
+    s = block_sum_tree<kThreads>(s);
     if (threadIdx.x == 0) D[e] = s;
 }
 
@@ -112,7 +98,7 @@ __global__ void __launch_bounds__(kThreads) k_slice_square_sums(size_t M, const 
     } else if (t == 0) {
         for (size_t m = threadIdx.x; m < M; m += kThreads) s = fma(v[m], v[m], s);
     }
-    s = block_sum(s);
+    s = block_sum_tree<kThreads>(s);
     if (threadIdx.x == 0) nrm[t] = s;
 }
 
@@ -127,14 +113,14 @@ __global__ void __launch_bounds__(kThreads) k_update(double* __restrict__ C, con
             const double x = D[((e / b) * n + t) * b + e % b];
             s = fma(x, x, s);
         }
-        const double step = block_sum(s) / nrm[t];
+        const double step = block_sum_tree<kThreads>(s) / nrm[t];
         for (size_t e = threadIdx.x; e < a * b; e += kThreads) {
             const size_t k = ((e / b) * n + t) * b + e % b;
             C[k] = fma(step, D[k], C[k]);
         }
     } else {
         for (size_t e = threadIdx.x; e < a * n * b; e += kThreads) s = fma(D[e], D[e], s);
-        const double pyr = block_sum(s);
+        const double pyr = block_sum_tree<kThreads>(s);
         double den = 0.0;
         for (size_t q = 0; q < n; ++q) den += nrm[q];
         const double step = pyr / den;
@@ -145,7 +131,7 @@ __global__ void __launch_bounds__(kThreads) k_update(double* __restrict__ C, con
 __global__ void __launch_bounds__(kThreads) k_sum_squares(size_t M, const double* __restrict__ v, double* __restrict__ out) {
     double s = 0.0;
     for (size_t m = threadIdx.x; m < M; m += kThreads) s = fma(v[m], v[m], s);
-    s = block_sum(s);
+    s = block_sum_tree<kThreads>(s);
     if (threadIdx.x == 0) out[0] = s;
 }
 

@@ -1,11 +1,14 @@
 // Device helpers shared by the iterations on the local operator (als_local.hip: CG, als_eig.hip: LOBPCG): the
-// launch shape of their vector kernels and the fixed-order sums that make every block hold the same scalar without a
-// grid barrier or a floating-point atomic.
+// launch shape of their vector kernels (CB, CMAXB, blocks_for) and the sum of the block partials in one fixed order
+// (sum_partials), which makes every block hold the same scalar without a grid barrier or a floating-point atomic.
+// The sum over a block itself is reduce_dev.hpp's block_sum_all, wave partials added sequentially from 0.0.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstddef>
+
+#include "reduce_dev.hpp"
 
 namespace xrs {
 namespace als_local {
@@ -16,13 +19,7 @@ constexpr int CMAXB = 1024;   // max blocks (= partial sums per reduction)
 // the block's sum, in every thread
 __device__ __forceinline__ double block_sum_all(double v) {
     __shared__ double part[CB / 64];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-#pragma unroll
-    for (int i = 0; i < CB / 64; ++i) s += part[i];
+    const double s = xrs::block_sum_all<Order::from_zero, CB / 64>(v, part);
     __syncthreads();
     return s;
 }

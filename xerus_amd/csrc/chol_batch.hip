@@ -3,6 +3,7 @@
 // below) and above (blocked, solve.hip chol_full) -- with the kernels' argument tables chunked here.
 #include <algorithm>
 
+#include "reduce_dev.hpp"
 #include "tt_common.hpp"
 
 namespace xrs {
@@ -41,13 +42,8 @@ __global__ void __launch_bounds__(256) k_split_shift(const BigArgs a) {
     const int j = blockIdx.y, n = a.n[j], n1 = 256, n2 = n - 256;
     const double* A = a.src[j];
     __shared__ double red[4];
-    double tr = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) tr += A[size_t(i) * n + i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) tr += __shfl_xor(tr, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = tr;
-    __syncthreads();
-    const double shift = a.shift[j] * (red[0] + red[1] + red[2] + red[3]);
+    block_trace<256>(A, n, red);
+    const double shift = a.shift[j] * sum_chain4(red);
     const size_t total = size_t(n) * n;
     for (size_t e = size_t(blockIdx.x) * 256 + threadIdx.x; e < total; e += size_t(gridDim.x) * 256) {
         const int r = int(e / n), c = int(e - size_t(r) * n);

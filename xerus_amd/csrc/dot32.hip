@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "reduce_dev.hpp"
 #include "runtime.hpp"
 #include "scratch_map.hpp"
 #include "sgemm.hpp"
@@ -45,10 +46,8 @@ __global__ void __launch_bounds__(256) k_dot32_finish(const float* __restrict__ 
     if (blockIdx.x < kPairBlocks) {
         double s = 0.0;
         for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += kPairBlocks * 256) s = fma(double(E[i]), double(F[i]), s);
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+        s = block_sum_t0<Order::pairwise4>(s, red);
+        if (threadIdx.x == 0) partial[blockIdx.x] = s;
         return;
     }
     const int c = int(blockIdx.x) - kPairBlocks;
@@ -63,9 +62,8 @@ __global__ void __launch_bounds__(256) k_dot32_finish(const float* __restrict__ 
     const unsigned* w = slots + size_t(c) * kCmaxSlots;
     unsigned m = 0u;
     for (int i = threadIdx.x; i < kCmaxSlots; i += 256) m = max(m, w[i]);
-    for (int o = 32; o > 0; o >>= 1) m = max(m, unsigned(__shfl_xor(int(m), o)));
-    if ((threadIdx.x & 63) == 0) redu[threadIdx.x >> 6] = m;
-    __syncthreads();
+    m = wave_max(m);
+    wave_partials(m, redu);
     if (threadIdx.x == 0) cmax_out[c] = max(max(redu[0], redu[1]), max(redu[2], redu[3]));
 }
 

@@ -6,6 +6,7 @@
 #include <cmath>
 
 #include "elementwise.hpp"
+#include "reduce_dev.hpp"
 #include "scratch_map.hpp"
 
 namespace xrs {
@@ -13,25 +14,12 @@ namespace xrs {
 constexpr int RB = 256;        // threads per reduction block
 constexpr int RMAXB = 1024;    // max partial blocks
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
+// the block's sum in thread 0 (the other threads return 0.0)
 __device__ __forceinline__ double block_sum(double v) {
     __shared__ double part[RB / 64];
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) part[w] = v;
+    const double s = block_sum_t0<Order::from_zero, RB / 64>(v, part);
     __syncthreads();
-    double s = 0.0;
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int i = 0; i < RB / 64; ++i) s += part[i];
-    }
-    __syncthreads();
-    return s;  // valid in thread 0
+    return s;
 }
 
 // Scaled sum of squares (Blue's three accumulators, as LAPACK 3.10's dnrm2): entries above kTbig / below kTsml are
@@ -179,11 +167,7 @@ __global__ void __launch_bounds__(256) k_amax_many(const AmaxArgs a, unsigned lo
         const unsigned long long b = static_cast<unsigned long long>(__double_as_longlong(fabs(x[i])));
         mx = b > mx ? b : mx;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long t = __shfl_xor(mx, o, 64);
-        mx = t > mx ? t : mx;
-    }
+    mx = wave_max(mx);
     if ((threadIdx.x & 63) == 0 && mx != 0) atomicMax(out + blockIdx.y, mx);
 }
 

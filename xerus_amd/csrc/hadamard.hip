@@ -16,6 +16,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "reduce_dev.hpp"
 #include "runtime.hpp"
 #include "scratch_map.hpp"
 
@@ -110,15 +111,7 @@ __global__ void __launch_bounds__(256) k_rank_one_argmax(const ArgmaxArgs g) {
             at = i;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ov = __shfl_xor(best, o, 64);
-        const uint32_t oi = __shfl_xor(at, o, 64);
-        if (ov > best || (ov == best && oi < at)) {
-            best = ov;
-            at = oi;
-        }
-    }
+    wave_arg_best(best, at, [](double a, double b) { return a > b; });
     if ((threadIdx.x & 63) == 0) {
         sv[threadIdx.x >> 6] = best;
         si[threadIdx.x >> 6] = at;

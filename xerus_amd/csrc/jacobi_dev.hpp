@@ -1,52 +1,18 @@
-// Device code shared by the one-sided Jacobi kernels (svd.hip, svd_batched.hip): DPP lane-group sums, 1/x and
+// Device code shared by the one-sided Jacobi kernels (svd.hip, svd_batched.hip): 1/x and
 // sqrt(x) from the hardware estimates, the rotation parameters and the stopping tolerance (every kernel), and the
 // one-workgroup solve of k_jacobi_vt_lds, k_jacobi_vt_global and k_svd_batched: the circle-tournament pairing
 // (circle_pair), the sweep / round loop with its stopping rule (jacobi_sweeps) and the row norms ranked
 // descending (jacobi_rank_rows). What rotates a row pair stays with each kernel: rotate_pair in svd.hip, rotate_rows (the
-// rows carry their accumulated rotations) in svd_batched.hip. Internal linkage: each kernel file gets its own copy.
+// rows carry their accumulated rotations) in svd_batched.hip. The DPP lane-group sums (dpp, gsum<G>) come from
+// reduce_dev.hpp. Internal linkage: each kernel file gets its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "reduce_dev.hpp"
 
 namespace xrs {
 
 namespace {
-
-// DPP move of a double (two 32-bit moves); CTRL is a DPP16 control word whose every lane has a valid
-// source (row rotations / mirrors / quad permutations), so no "old" value is needed (mov_dpp: no
-// zero-initialised destination, which update_dpp(0, ...) costs two extra moves per double)
-template <int CTRL>
-__device__ __forceinline__ double dpp(double v) {
-    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-
-
-// Sum over a group of G (8, 16 or 32) consecutive lanes. Every lane of the group ends with the same bits:
-// each step adds two values that are equal up to the order of operands of commutative adds.
-//   G = 16: row_ror 8, 4, 2, 1 (rotations of an increasingly periodic sequence)
-//   G = 8:  row_half_mirror (i <-> 7-i), quad_perm [2,3,0,1] (i <-> i^2), quad_perm [1,0,3,2] (i <-> i^1)
-template <int G>
-__device__ __forceinline__ double gsum(double v) {
-    if constexpr (G == 16 || G == 32) {
-        v += dpp<0x128>(v);
-        v += dpp<0x124>(v);
-        v += dpp<0x122>(v);
-        v += dpp<0x121>(v);
-        if constexpr (G == 32) {   // the two DPP rows of the group: the two results of v_permlane16_swap(v, v)
-            // are {own, partner} on every lane, so their sum is the pair sum without a per-lane select
-            const auto lo = __builtin_amdgcn_permlane16_swap(__double2loint(v), __double2loint(v), false, false);
-            const auto hi = __builtin_amdgcn_permlane16_swap(__double2hiint(v), __double2hiint(v), false, false);
-            v = __hiloint2double(hi[0], lo[0]) + __hiloint2double(hi[1], lo[1]);
-        }
-    } else {
-        static_assert(G == 8, "groups of 8 or 16 lanes");
-        v += dpp<0x141>(v);
-        v += dpp<0x4E>(v);
-        v += dpp<0xB1>(v);
-    }
-    return v;
-}
 
 // 1/x and sqrt(x) to ~1 ulp from the hardware estimates + Newton steps (rotation parameters only need
 // to be mutually consistent; no IEEE division / square-root sequences in the per-round critical path)

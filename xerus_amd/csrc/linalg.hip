@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "reduce_dev.hpp"
 #include "scratch_map.hpp"
 #include "smallla.hpp"
 
@@ -48,18 +49,8 @@ __global__ void __launch_bounds__(256) k_dev_identity(const double* __restrict__
         const double d = fabs(G[e] - ((e / n) == (e % n) ? 1.0 : 0.0));
         mx = (d > mx || d != d) ? d : mx;   // NaN propagates
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double t = __shfl_xor(mx, o, 64);
-        mx = (t > mx || t != t) ? t : mx;
-    }
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double m = red[0];
-        for (int i = 1; i < 4; ++i) m = (red[i] > m || red[i] != red[i]) ? red[i] : m;
-        out[0] = m;
-    }
+    mx = block_max_nan_t0(mx, red);
+    if (threadIdx.x == 0) out[0] = mx;
 }
 
 // First-order second CholeskyQR pass: G2 = I + E with ||E|| tiny -> L2 = I + Elow + O(E^2),
@@ -77,18 +68,8 @@ __global__ void __launch_bounds__(256) k_first_order(const double* __restrict__ 
         L2[e] = (i == j ? 1.0 : 0.0) + el;
         Li2[e] = (i == j ? 1.0 : 0.0) - el;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double t = __shfl_xor(mx, o, 64);
-        mx = (t > mx || t != t) ? t : mx;
-    }
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double m = red[0];
-        for (int i = 1; i < 4; ++i) m = (red[i] > m || red[i] != red[i]) ? red[i] : m;
-        emax[blockIdx.x] = m;
-    }
+    mx = block_max_nan_t0(mx, red);
+    if (threadIdx.x == 0) emax[blockIdx.x] = mx;
 }
 
 static double max_abs_dev_identity(xrs_handle_t h, const double* G, size_t n) {

@@ -39,6 +39,7 @@
 
 #include <hip/hip_ext.h>
 
+#include "reduce_dev.hpp"
 #include "sgemm.hpp"
 
 #ifdef XRS_SG_STAMPS
@@ -213,19 +214,6 @@ struct Args {
     int xcd;   // 1: tiles sharing a B column panel on one XCD, 2: sharing an A row panel, 0: column-major
 };
 
-// an fp64 max|.| as a float for the max slots: above FLT_MAX -> inf, a nonzero max below the fp32 range -> the
-// smallest denormal (so that the check sees it as out of range, not as a zero core)
-__device__ __forceinline__ float fp64_max_as_float(double m) {
-    const float f = float(m);
-    return (m > 0.0 && f == 0.0f) ? __uint_as_float(1u) : f;
-}
-
-__device__ __forceinline__ void wave_max_atomic(unsigned* w, float m) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    if ((threadIdx.x & 63) == 0) atomicMax(w, __float_as_uint(m));
-}
-
 // value of a max word: the maximum of its kMaxLanes lanes (wave-uniform loads)
 __device__ __forceinline__ unsigned max_word(const unsigned* __restrict__ w) {
     unsigned m = 0u;
@@ -237,8 +225,7 @@ __device__ __forceinline__ unsigned max_word(const unsigned* __restrict__ w) {
 // workgroup max of m (every thread of the workgroup calls it; `red` holds >= 16 words of LDS that are free)
 // into lane (workgroup id % kMaxLanes) of the max word w
 __device__ __forceinline__ void block_max_atomic(unsigned* w, float m, float* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    m = wave_fmaxf(m);
     const int nw = int(blockDim.x) >> 6;
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
     __syncthreads();

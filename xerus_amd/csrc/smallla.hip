@@ -15,6 +15,8 @@
 //             round-robin parallel ordering, rotations accumulated in J (U = J^T).
 #include "smallla.hpp"
 
+#include "reduce_dev.hpp"
+
 #include <cstdio>
 
 namespace xrs {
@@ -54,14 +56,8 @@ __device__ __forceinline__ void potrf32_body(double* __restrict__ G, int n, doub
     double* dummy = Dinv + size_t(n + 31) * NB + (tid & 31);   // padding row of Dinv: sink for masked stores
     if (tid == 0) fail = 0;
     // trace(G) -> absolute shift (shift_rel * trace), no host round trip
-    double tr = 0.0;
-    for (int i = tid; i < n; i += POT_THREADS) tr += G[size_t(i) * n + i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) tr += __shfl_xor(tr, o, 64);
-    if (lane == 0) red[wave] = tr;
-    __syncthreads();
-    tr = 0.0;
-    for (int w = 0; w < POT_THREADS / 64; ++w) tr += red[w];
+    block_trace<POT_THREADS>(G, n, red);
+    const double tr = sum_from_zero<POT_THREADS / 64>(red);
     if (tid == 0 && info) info[0] = tr;
     const double shift = shift_rel * tr;
     if (shift != 0.0)
@@ -405,15 +401,8 @@ __device__ __forceinline__ void potrf_rr_body(double* __restrict__ G, int n, dou
     const int ntiles = T * (T + 1) / 2;
     if (tid == 0) fail = 0;
     PSTAMP(0);
-    double tr = 0.0;
-    for (int i = tid; i < n; i += PR_THREADS) tr += S[size_t(i) * n + i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) tr += __shfl_xor(tr, o, 64);
-    if (lane == 0) red[wave] = tr;
-    __syncthreads();
-    tr = 0.0;
-#pragma unroll
-    for (int w = 0; w < PR_WAVES; ++w) tr += red[w];
+    block_trace<PR_THREADS>(S, n, red);
+    const double tr = sum_from_zero<PR_WAVES>(red);
     if (tid == 0 && info) info[0] = tr;
     const double shift = shift_rel * tr;
 
@@ -601,15 +590,8 @@ __device__ __forceinline__ void potrf_la_body(double* __restrict__ G, int n, dou
     const int ntiles = T * (T + 1) / 2;
     if (tid == 0) fail = 0;
     PSTAMP(0);
-    double tr = 0.0;
-    for (int i = tid; i < n; i += LA_THREADS) tr += S[size_t(i) * n + i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) tr += __shfl_xor(tr, o, 64);
-    if (lane == 0) red[wave] = tr;
-    __syncthreads();
-    tr = 0.0;
-#pragma unroll
-    for (int w = 0; w < LA_WAVES; ++w) tr += red[w];
+    block_trace<LA_THREADS>(S, n, red);
+    const double tr = sum_from_zero<LA_WAVES>(red);
     if (tid == 0 && info) info[0] = tr;
     const double shift = shift_rel * tr;
 
@@ -885,16 +867,10 @@ __global__ void __launch_bounds__(256) k_trinv_batched(const TrinvBatch b, int d
 
 // ---------------------------------------------------------------------------------------------
 // Block reductions for the single-workgroup kernels (1024 threads).
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // sum over the whole workgroup; every thread gets the result
 __device__ double bsum(double v, double* red) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    v = wsum(v);
+    v = wave_sum(v);
     __syncthreads();
     if (lane == 0) red[w] = v;
     __syncthreads();
@@ -924,7 +900,7 @@ __global__ void __launch_bounds__(1024) k_qrcp(double* __restrict__ W, int m, in
         const double* col = W + size_t(j) * m;
         double s = 0.0;
         for (int i = lane; i < m; i += 64) s += col[i] * col[i];
-        s = wsum(s);
+        s = wave_sum(s);
         if (lane == 0) {
             vn1[j] = sqrt(s);
             vn2[j] = vn1[j];
@@ -944,12 +920,7 @@ __global__ void __launch_bounds__(1024) k_qrcp(double* __restrict__ W, int m, in
             const double v = vn1[j];
             if (v > best || (v == best && j < bi)) { best = v; bi = j; }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const double ov = __shfl_xor(best, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-        }
+        wave_arg_best(best, bi, [](double a, double b) { return a > b; });
         if (lane == 0) { sh_val[wave] = best; sh_idx[wave] = bi; }
         __syncthreads();
         if (tid == 0) {
@@ -1013,7 +984,7 @@ __global__ void __launch_bounds__(1024) k_qrcp(double* __restrict__ W, int m, in
                 double* cj = W + size_t(j) * m;
                 double d = (lane == 0) ? cj[k] : 0.0;
                 for (int i = k + 1 + lane; i < m; i += 64) d += ck[i] * cj[i];
-                d = wsum(d) * tk;
+                d = wave_sum(d) * tk;
                 if (lane == 0) cj[k] -= d;
                 for (int i = k + 1 + lane; i < m; i += 64) cj[i] -= d * ck[i];
             }
@@ -1031,7 +1002,7 @@ __global__ void __launch_bounds__(1024) k_qrcp(double* __restrict__ W, int m, in
                 if (temp2 <= tol3z) {
                     double s2 = 0.0;
                     for (int i = k + 1 + lane; i < m; i += 64) s2 += cj[i] * cj[i];
-                    s2 = wsum(s2);
+                    s2 = wave_sum(s2);
                     if (lane == 0) {
                         const double nv = (k + 1 < m) ? sqrt(s2) : 0.0;
                         vn1[j] = nv;
@@ -1077,7 +1048,7 @@ __global__ void __launch_bounds__(1024) k_qrcp(double* __restrict__ W, int m, in
         for (int j = i + wave; j < kmax; j += 16) {
             double d = (lane == 0) ? Q[size_t(i) * kmax + j] : 0.0;
             for (int r = i + 1 + lane; r < m; r += 64) d += v[r] * Q[size_t(r) * kmax + j];
-            d = wsum(d) * ti;
+            d = wave_sum(d) * ti;
             if (lane == 0) Q[size_t(i) * kmax + j] -= d;
             for (int r = i + 1 + lane; r < m; r += 64) Q[size_t(r) * kmax + j] -= d * v[r];
         }
@@ -1114,7 +1085,7 @@ __global__ void __launch_bounds__(1024) k_jacobi(double* __restrict__ W, int p, 
                     const double x = wi[k], y = wj[k];
                     a += x * x; b += y * y; c += x * y;
                 }
-                a = wsum(a); b = wsum(b); c = wsum(c);
+                a = wave_sum(a); b = wave_sum(b); c = wave_sum(c);
                 if (fabs(c) > tol * sqrt(a * b) && c != 0.0) {
                     const double zeta = (b - a) / (2.0 * c);
                     const double t_ = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
@@ -1163,7 +1134,7 @@ __global__ void __launch_bounds__(1024) k_svd_finish(const double* __restrict__ 
         const double* w = Wr + size_t(i) * q;
         double s = 0.0;
         for (int k = lane; k < q; k += 64) s += w[k] * w[k];
-        s = wsum(s);
+        s = wave_sum(s);
         if (lane == 0) sn[i] = sqrt(s);
     }
     __syncthreads();

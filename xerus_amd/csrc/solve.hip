@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <vector>
 
+#include "reduce_dev.hpp"
 #include "smallla.hpp"
 
 namespace xrs {
@@ -42,11 +43,9 @@ void copy2d(xrs_handle_t h, double* dst, size_t ldd, const double* src, size_t l
 __global__ void __launch_bounds__(256) k_max_partial(const double* __restrict__ A, size_t total, double* __restrict__ part) {
     double m = 0.0;
     for (size_t e = size_t(blockIdx.x) * 256 + threadIdx.x; e < total; e += size_t(gridDim.x) * 256) m = fmax(m, A[e]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
+    m = wave_fmax(m);
     __shared__ double red[4];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
+    wave_partials(m, red);
     if (threadIdx.x == 0) part[blockIdx.x] = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
 }
 
@@ -116,13 +115,8 @@ namespace {
 // W[i][i] += rel * trace(W) (one workgroup; the shifted factorisations of the certificates)
 __global__ void __launch_bounds__(256) k_shift_diag(double* __restrict__ W, size_t n, double rel) {
     __shared__ double red[4];
-    double tr = 0.0;
-    for (size_t i = threadIdx.x; i < n; i += 256) tr += W[i * n + i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) tr += __shfl_xor(tr, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = tr;
-    __syncthreads();
-    const double s = rel * ((red[0] + red[1]) + (red[2] + red[3]));
+    block_trace<256>(W, n, red);
+    const double s = rel * sum_pairwise4(red);
     for (size_t i = threadIdx.x; i < n; i += 256) W[i * n + i] += s;
 }
 }  // namespace

@@ -482,10 +482,7 @@ __global__ void __launch_bounds__(BR * G) k_jacobi_vt_blocks(const double* __res
             const double sj = __hip_atomic_load(&norms[j2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             rk += (sj > si) || (sj == si && j2 < row);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) rk += __shfl_xor(rk, o, 64);
-        if ((tid & 63) == 0) part[tid >> 6] = rk;
-        __syncthreads();
+        wave_partials(wave_sum(rk), part);
         int rank = 0;
 #pragma unroll
         for (int i = 0; i < NT / 64; ++i) rank += part[i];

@@ -99,13 +99,8 @@ __global__ void __launch_bounds__(SB_THREADS) k_svd_batched(const double* __rest
         const double v = fabs(Ab[e]);
         mx = v > mx ? v : mx;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double t = __shfl_xor(mx, o, 64);
-        mx = t > mx ? t : mx;
-    }
-    if ((tid & 63) == 0) red[tid >> 6] = mx;
-    __syncthreads();
+    mx = wave_max_gt(mx);
+    wave_partials(mx, red);
     mx = red[0];
     for (int i = 1; i < NT / 64; ++i) mx = red[i] > mx ? red[i] : mx;
     const int ex = (mx > 0.0 && mx <= 1.7976931348623157e308) ? ilogb(mx) : 0;
@@ -192,12 +187,11 @@ __device__ __forceinline__ void cb_sync() {
 }
 
 __device__ __forceinline__ double cb_block_sum(double v, double* red4) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    v = wave_sum(v);
     cb_sync();   // (red4 may still be read from the previous call)
     if ((threadIdx.x & 63) == 0) red4[threadIdx.x >> 6] = v;
     cb_sync();
-    return (red4[0] + red4[1]) + (red4[2] + red4[3]);
+    return sum_pairwise4(red4);
 }
 
 // (X is not __restrict__: other threads write what this one reads, across the barriers)
@@ -225,15 +219,7 @@ __global__ void __launch_bounds__(CB_THREADS) k_orthonormalise(double* X, int k,
                         bc = c;
                     }
                 }
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) {
-                    const double ov = __shfl_xor(bv, o, 64);
-                    const int oc = __shfl_xor(bc, o, 64);
-                    if (ov < bv || (ov == bv && oc < bc)) {
-                        bv = ov;
-                        bc = oc;
-                    }
-                }
+                wave_arg_best(bv, bc, [](double a, double b) { return a < b; });
                 cb_sync();   // (best_* may still be read from an earlier vector)
                 if (lane == 0) {
                     best_v[wave] = bv;
@@ -256,8 +242,7 @@ __global__ void __launch_bounds__(CB_THREADS) k_orthonormalise(double* X, int k,
                 for (int r = wave; r < z; r += WAVES) {
                     double s = 0.0;
                     for (int c = lane; c < n; c += 64) s = fma(at(r, c), at(z, c), s);
-#pragma unroll
-                    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+                    s = wave_sum(s);
                     if (lane == 0) d[r] = s;
                 }
                 cb_sync();

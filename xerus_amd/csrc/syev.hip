@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "scratch_map.hpp"
+#include "reduce_dev.hpp"
 #include "smallla.hpp"
 
 namespace xrs {
@@ -44,38 +45,6 @@ namespace xrs {
 namespace {
 
 constexpr int SY_MAX = 256;
-
-// Cross-lane sums without the LDS crossbar (a __shfl_xor of a double is two ds_bpermute round trips, the
-// bulk of a column step when chained): DPP row rotations within 16 lanes, v_permlane16_swap across the
-// two rows of a 32-lane half, v_permlane32_swap across the halves.
-template <int CTRL>
-__device__ __forceinline__ double dpp(double v) {
-    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double sum16(double v) {   // every lane of the 16-lane row gets the row's sum
-    v += dpp<0x128>(v);
-    v += dpp<0x124>(v);
-    v += dpp<0x122>(v);
-    v += dpp<0x121>(v);
-    return v;
-}
-// v + (the value of lane l ^ 16): the two results of v_permlane16_swap(v, v) are {own, partner} on every lane
-// (odd rows get the even rows in the first, even rows the odd rows in the second), so their sum is the pair
-// sum without the per-lane select -- one dependent operation less per level, bit-identical (a + b = b + a)
-__device__ __forceinline__ double addx16(double v) {
-    const auto lo = __builtin_amdgcn_permlane16_swap(__double2loint(v), __double2loint(v), false, false);
-    const auto hi = __builtin_amdgcn_permlane16_swap(__double2hiint(v), __double2hiint(v), false, false);
-    return __hiloint2double(hi[0], lo[0]) + __hiloint2double(hi[1], lo[1]);
-}
-__device__ __forceinline__ double addx32(double v) {   // v + (the value of lane l ^ 32), v_permlane32_swap
-    const auto lo = __builtin_amdgcn_permlane32_swap(__double2loint(v), __double2loint(v), false, false);
-    const auto hi = __builtin_amdgcn_permlane32_swap(__double2hiint(v), __double2hiint(v), false, false);
-    return __hiloint2double(hi[0], lo[0]) + __hiloint2double(hi[1], lo[1]);
-}
-__device__ __forceinline__ double sum32(double v) { return addx16(sum16(v)); }
-__device__ __forceinline__ double sum64(double v) { return addx32(sum32(v)); }
 
 // workgroup barrier for LDS hand-offs only: waits for this wave's LDS operations, not for its global
 // stores (__syncthreads' release fence would drain the per-column stores of the reflectors, d, e and tau
@@ -160,7 +129,7 @@ __global__ void __launch_bounds__(GRID * GRID) k_sytrd(const double* __restrict_
                 const int i = lane + 64 * q;
                 if (i >= j + 2 && i < n) s = fma(x[q], x[q], s);
             }
-            s = sum64(s);
+            s = gsum<64>(s);
             double tv = 0.0, beta = alpha, scal = 0.0;
             if (s > 0.0) {
                 beta = -copysign(sqrt(fma(alpha, alpha, s)), alpha);
@@ -233,7 +202,7 @@ __global__ void __launch_bounds__(GRID * GRID) k_sytrd(const double* __restrict_
         double sk = 0.0;
 #pragma unroll
         for (int i = lane; i < NP; i += 64) sk = fma(ps[i], vs[i], sk);
-        const double K = -0.5 * tj * sum64(sk);
+        const double K = -0.5 * tj * gsum<64>(sk);
         // (e) A -= v w^T + w v^T (v, w vanish at indices <= j: finished rows and columns stay untouched), on
         //     the active blocks only: block rows / columns below (j + 1) / GRID are finished, so one
         //     compile-time loop nest per first active block (a switch, not per-block branches)
@@ -352,7 +321,7 @@ __global__ void __launch_bounds__(512) k_sytrd_l512(const double* __restrict__ A
                 const int i = lane + 64 * q;
                 if (i >= j + 2 && i < n) s = fma(x[q], x[q], s);
             }
-            s = sum64(s);
+            s = gsum<64>(s);
             double tv = 0.0, beta = alpha, scal = 0.0;
             if (s > 0.0) {
                 beta = -copysign(sqrt(fma(alpha, alpha, s)), alpha);
@@ -427,7 +396,7 @@ __global__ void __launch_bounds__(512) k_sytrd_l512(const double* __restrict__ A
             }
 #pragma unroll
             for (int ia = IA0; ia < NR; ++ia) {
-                const double r = sum16(rp[ia]);
+                const double r = gsum<16>(rp[ia]);
                 if (tc == 0) psr[tr + 32 * ia] = r;
             }
             L512_STAMP(4);
@@ -446,7 +415,7 @@ __global__ void __launch_bounds__(512) k_sytrd_l512(const double* __restrict__ A
             double sk = 0.0;
 #pragma unroll
             for (int q = 0; q < NP / 64; ++q) sk = fma(ps[lane + 64 * q], vs[lane + 64 * q], sk);
-            const double K = -0.5 * tj * sum64(sk);
+            const double K = -0.5 * tj * gsum<64>(sk);
             double vi[NR], wi[NR];
 #pragma unroll
             for (int ia = IA0; ia < NR; ++ia) {
@@ -550,13 +519,10 @@ __global__ void __launch_bounds__(64 * SW_WAVES) k_stebz_stein(const double* __r
         emax2 = fmax(emax2, ei * ei);
         amax = fmax(amax, fabs(di) + r);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        gl = fmin(gl, __shfl_xor(gl, o, 64));
-        gu = fmax(gu, __shfl_xor(gu, o, 64));
-        emax2 = fmax(emax2, __shfl_xor(emax2, o, 64));
-        amax = fmax(amax, __shfl_xor(amax, o, 64));
-    }
+    gl = wave_fmin(gl);
+    gu = wave_fmax(gu);
+    emax2 = wave_fmax(emax2);
+    amax = wave_fmax(amax);
     // the multisection's three-term recurrence runs on T scaled by a power of two (exact: the counts are
     // those of T) so that |d - x| and e^2 stay O(1) and 4 levels cannot overflow between rescalings
     const double tsc = ldexp(1.0, -ilogb(fmax(amax, 1e-300)));
@@ -615,11 +581,8 @@ __global__ void __launch_bounds__(64 * SW_WAVES) k_stebz_stein(const double* __r
             pm1 = pv;
         }
         double nlo = c <= m ? x : -1e300, nhi = c >= m + 1 ? x : 1e300;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            nlo = fmax(nlo, __shfl_xor(nlo, o, 64));
-            nhi = fmin(nhi, __shfl_xor(nhi, o, 64));
-        }
+        nlo = wave_fmax(nlo);
+        nhi = wave_fmin(nhi);
         if (lane == 0) {
             rlo[rounds & 1][wave] = nlo;
             rhi[rounds & 1][wave] = nhi;
@@ -780,15 +743,14 @@ __global__ void __launch_bounds__(64 * SW_WAVES) k_stebz_stein(const double* __r
         // normalise (scaled 2-norm over the wave)
         double mx = 0.0;
         for (int i = lane; i < n; i += 64) mx = fmax(mx, fabs(lb[i]));
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
+        mx = wave_fmax(mx);
         const double inv_mx = mx > 0.0 ? 1.0 / mx : 1.0;
         double ss = 0.0;
         for (int i = lane; i < n; i += 64) {
             const double v = lb[i] * inv_mx;
             ss = fma(v, v, ss);
         }
-        ss = sum64(ss);
+        ss = gsum<64>(ss);
         const double sc = inv_mx / sqrt(ss);
         __syncthreads();
         if (wave == 0)   // (every wave formed the same scale)
@@ -847,7 +809,7 @@ __global__ void __launch_bounds__(256) k_ormtr(const double* __restrict__ V, con
                 if (s & 1) d1 = fma(vv[s], z[s], d1);
                 else d0 = fma(vv[s], z[s], d0);
             }
-            const double f = st[j] * sum64(d0 + d1);
+            const double f = st[j] * gsum<64>(d0 + d1);
 #pragma unroll
             for (int s = 0; s < ZE; ++s) z[s] = fma(-f, vv[s], z[s]);
         }
@@ -882,21 +844,19 @@ __global__ void __launch_bounds__(256) k_cluster_orth(const double* __restrict__
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     double a = 0.0;
     for (int i = tid; i < n; i += 256) a = fmax(a, fabs(d[i]) + (i > 0 ? fabs(e[i - 1]) : 0.0) + (i + 1 < n ? fabs(e[i]) : 0.0));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a = fmax(a, __shfl_xor(a, o, 64));
-    if (lane == 0) red[wave] = a;
-    __syncthreads();
+    a = wave_fmax(a);
+    wave_partials(a, red);
     if (tid == 0) tnorm = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
     __syncthreads();
     const double ortol = 1e-3 * tnorm;
     auto dot = [&](const double* x, const double* y) {
         double s = 0.0;
         for (int i = tid; i < n; i += 256) s = fma(x[i], y[i], s);
-        s = sum64(s);
+        s = gsum<64>(s);
         __syncthreads();
         if (lane == 0) red[wave] = s;
         __syncthreads();
-        return (red[0] + red[1]) + (red[2] + red[3]);
+        return sum_pairwise4(red);
     };
     int c0 = 0;
     while (c0 < kk) {
@@ -1001,8 +961,7 @@ __global__ void __launch_bounds__(512) k_gebrd_sq(const double* __restrict__ A, 
             x[i][k] = (r < n && c < n) ? A[size_t(r) * n + c] : 0.0;
             am = fmax(am, fabs(x[i][k]));
         }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) am = fmax(am, __shfl_xor(am, o, 64));
+    am = wave_fmax(am);
     if (lane == 0) red[wave] = am;
     for (int i = tid; i < 2 * n; i += 512) tgd[i] = 0.0;
     lds_barrier();
@@ -1037,8 +996,8 @@ __global__ void __launch_bounds__(512) k_gebrd_sq(const double* __restrict__ A, 
                 ss = (r > j) ? fma(y[i], y[i], ss) : ss;
                 al = (r == j) ? y[i] : al;
             }
-            ss = sum16(ss);
-            al = sum16(al);
+            ss = gsum<16>(ss);
+            al = gsum<16>(al);
             double beta, tau, sc;
             bd_reflector(al, ss, beta, tau, sc);
 #pragma unroll
@@ -1078,7 +1037,7 @@ __global__ void __launch_bounds__(512) k_gebrd_sq(const double* __restrict__ A, 
             }
 #pragma unroll
             for (int k = 0; k < 4; ++k)
-                if (32 * k + 31 > j) w[k] = (gam + 32 * k > j) ? sum16(w[k]) * taul : 0.0;
+                if (32 * k + 31 > j) w[k] = (gam + 32 * k > j) ? gsum<16>(w[k]) * taul : 0.0;
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 if (32 * k + 31 > j)
@@ -1221,8 +1180,8 @@ __global__ void __launch_bounds__(256) k_gk_split(const double* __restrict__ Z, 
         su = fma(u, u, su);
         sv = fma(v, v, sv);
     }
-    su = sum64(su);
-    sv = sum64(sv);
+    su = gsum<64>(su);
+    sv = gsum<64>(sv);
     const double iu = su > 0.0 ? 1.0 / sqrt(su) : 0.0, iv = sv > 0.0 ? 1.0 / sqrt(sv) : 0.0;
     for (int k = lane; k < n; k += 64) {
         Vb[size_t(q) * n + k] = z[2 * k] * iv;
@@ -1255,10 +1214,8 @@ __global__ void __launch_bounds__(1024) k_svd_check(const double* __restrict__ P
     const int w = threadIdx.x >> 6;
     double am = 0.0;
     for (int e = threadIdx.x; e < n * n; e += 1024) am = fmax(am, fabs(A[e]));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) am = fmax(am, __shfl_xor(am, o, 64));
-    if ((threadIdx.x & 63) == 0) red[0][w] = am;
-    __syncthreads();
+    am = wave_fmax(am);
+    wave_partials(am, red[0]);
     if (threadIdx.x == 0) {
         double v = 0.0;
         for (int i = 0; i < 16; ++i) v = fmax(v, red[0][i]);
@@ -1275,13 +1232,10 @@ __global__ void __launch_bounds__(1024) k_svd_check(const double* __restrict__ P
         m1 = (g1 > m1 || g1 != g1) ? (g1 != g1 ? INFINITY : g1) : m1;
         m2 = (g2 > m2 || g2 != g2) ? (g2 != g2 ? INFINITY : g2) : m2;
     }
-    r2 = sum64(r2);
-    a2 = sum64(a2);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        m1 = fmax(m1, __shfl_xor(m1, o, 64));
-        m2 = fmax(m2, __shfl_xor(m2, o, 64));
-    }
+    r2 = gsum<64>(r2);
+    a2 = gsum<64>(a2);
+    m1 = wave_fmax(m1);
+    m2 = wave_fmax(m2);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) {
         red[0][w] = r2;

@@ -23,6 +23,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "reduce_dev.hpp"
 #include "runtime.hpp"
 #include "tt_common.hpp"
 
@@ -38,11 +39,7 @@ __device__ __forceinline__ bool aligned16(const void* p) { return (reinterpret_c
 
 // sum over the 256 threads of a workgroup (red: 4 doubles of LDS); every thread returns the sum
 __device__ __forceinline__ double block_sum(double v, double* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = (red[0] + red[1]) + (red[2] + red[3]);
+    v = block_sum_all<Order::pairwise4>(v, red);
     __syncthreads();
     return v;
 }
@@ -75,12 +72,8 @@ __global__ void __launch_bounds__(256) k_tangent_cert(const CertArgs a, double e
         mn = p2 < mn ? p2 : mn;
     }
     if (nan) mn = -1.0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double x = __shfl_xor(mx, o, 64), y = __shfl_xor(mn, o, 64);
-        mx = x > mx ? x : mx;
-        mn = y < mn ? y : mn;
-    }
+    mx = wave_max_gt(mx);
+    mn = wave_min_lt(mn);
     if ((threadIdx.x & 63) == 0) {
         smx[threadIdx.x >> 6] = mx;
         smn[threadIdx.x >> 6] = mn;

@@ -30,6 +30,7 @@
 #include <string>
 #include <vector>
 
+#include "reduce_dev.hpp"
 #include "tt_common.hpp"
 
 namespace xrs {
@@ -330,18 +331,8 @@ __global__ void __launch_bounds__(256) k_dev_identity_many(const DevIdArgs args)
         const double v = fabs(G[e] - ((e / n) == (e % n) ? 1.0 : 0.0));
         mx = (v > mx || v != v) ? v : mx;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double q = __shfl_xor(mx, o, 64);
-        mx = (q > mx || q != q) ? q : mx;
-    }
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double m = red[0];
-        for (int i = 1; i < 4; ++i) m = (red[i] > m || red[i] != red[i]) ? red[i] : m;
-        args.out[blockIdx.x * gridDim.y + blockIdx.y] = m;
-    }
+    mx = block_max_nan_t0(mx, red);
+    if (threadIdx.x == 0) args.out[blockIdx.x * gridDim.y + blockIdx.y] = mx;
 }
 
 void rl_sweep(TT& t, const size_t* max_ranks, double eps, double cX, size_t from);

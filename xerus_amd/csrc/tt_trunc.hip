@@ -26,6 +26,7 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "reduce_dev.hpp"
 #include "tt_common.hpp"
 
 namespace xrs {
@@ -426,12 +427,8 @@ __global__ void __launch_bounds__(256) k_rank_cert(const double* __restrict__ W,
     __shared__ double red[4];
     double s = 0.0;
     for (int e = threadIdx.x; e < n * n; e += 256) s = fma(W[e], W[e], s);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
+    const double w2 = block_sum_t0<Order::pairwise4>(s, red);
     if (threadIdx.x == 0) {
-        const double w2 = (red[0] + red[1]) + (red[2] + red[3]);
         // 1 / ||W|| > c ||A||  <=>  c^2 ||W||^2 ||A||^2 < 1  (NaN -> flagged)
         flag[0] = (c * c * w2 * trG[0] < 1.0) ? 0 : 1;
     }
@@ -477,9 +474,8 @@ __global__ void __launch_bounds__(256) k_pad_diag(double* __restrict__ G, int N,
     double v = 0.0;
     if (fill) {
         for (int p = t; p < N; p += 256) v = fmax(v, G[size_t(p) * N + p]);
-        for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-        if (lane == 0) red[w] = v;
-        __syncthreads();
+        v = wave_fmax(v);
+        wave_partials(v, red);
         v = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
         if (!(v > 0.0)) v = 1.0;
     }
@@ -494,18 +490,15 @@ __global__ void __launch_bounds__(256) k_rank_cert_gram(const double* __restrict
     double s = 0.0, tr = 0.0;
     for (int e = threadIdx.x; e < n * n; e += 256) s = fma(W[e], W[e], s);
     for (int i = threadIdx.x; i < n; i += 256) tr += G[size_t(i) * n + i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        s += __shfl_xor(s, o, 64);
-        tr += __shfl_xor(tr, o, 64);
-    }
+    s = wave_sum(s);
+    tr = wave_sum(tr);
     if ((threadIdx.x & 63) == 0) {
         red[threadIdx.x >> 6] = s;
         red[4 + (threadIdx.x >> 6)] = tr;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const double w2 = (red[0] + red[1]) + (red[2] + red[3]), t2 = (red[4] + red[5]) + (red[6] + red[7]);
+        const double w2 = sum_pairwise4(red), t2 = sum_pairwise4(red + 4);
         flag[0] = (c * c * w2 * t2 < 1.0) ? 0 : 1;
     }
 }

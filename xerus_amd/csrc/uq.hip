@@ -19,6 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "reduce_dev.hpp"
 #include "scratch_map.hpp"
 
 namespace xrs {
@@ -248,21 +249,6 @@ __global__ void __launch_bounds__(kThreads) k_congruence_mfma(size_t N, const do
     }
 }
 
-// fixed-order sum of the block's partial values (every thread returns the total)
-__device__ double block_sum(double v) {
-    __shared__ double red[kThreads];
-    red[threadIdx.x] = v;
-    __syncthreads();
-#pragma unroll
-    for (int o = kThreads / 2; o > 0; o >>= 1) {
-        if (int(threadIdx.x) < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    const double t = red[0];
-    __syncthreads();
-    return t;
-}
-
 // (L_j v_j)[c]
 __device__ __forceinline__ double symv_entry(const double* __restrict__ L, const double* __restrict__ V, size_t j, size_t c, size_t a) {
     const double* v = V + j * a;
@@ -288,14 +274,14 @@ __global__ void __launch_bounds__(kThreads) k_quadform_partial(size_t N, const d
         const size_t j = e / a;
         s = fma(V[e], symv_entry(L, V, j, e - j * a, a), s);
     }
-    s = block_sum(s);
+    s = block_sum_tree<kThreads>(s);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
 __global__ void __launch_bounds__(kThreads) k_sum_partials(int count, const double* __restrict__ partial, double* __restrict__ out) {
     double s = 0.0;
     for (int i = int(threadIdx.x); i < count; i += kThreads) s += partial[i];
-    s = block_sum(s);
+    s = block_sum_tree<kThreads>(s);
     if (threadIdx.x == 0) out[0] = s;
 }
 
@@ -313,7 +299,7 @@ __global__ void __launch_bounds__(kThreads) k_column_mean(size_t N, const double
     const size_t c = blockIdx.x;
     double s = 0.0;
     for (size_t j = threadIdx.x; j < N; j += kThreads) s += S[j * n + c];
-    s = block_sum(s);
+    s = block_sum_tree<kThreads>(s);
     if (threadIdx.x == 0) out[c] = s / double(N);
 }
 

@@ -37,6 +37,7 @@
 #include <utility>
 #include <vector>
 
+#include "reduce_dev.hpp"
 #include "runtime.hpp"
 #include "scratch_map.hpp"
 #include "sgemm.hpp"
@@ -67,25 +68,9 @@ __host__ __device__ __forceinline__ int f32_exp(int w) {
 }
 __device__ __forceinline__ float pow2f(int e) { return __uint_as_float(unsigned(127 + e) << 23); }   // e in [-126, 127]
 
-__device__ __forceinline__ float fp64_max_as_float(double m) {
-    const float f = float(m);
-    return (m > 0.0 && f == 0.0f) ? __uint_as_float(1u) : f;
-}
-__device__ __forceinline__ void wave_max_slot(unsigned* slot, double m) {
-    float f = fp64_max_as_float(m);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) f = fmaxf(f, __shfl_xor(f, o));
-    if ((threadIdx.x & 63) == 0) atomicMax(slot, __float_as_uint(f));
-}
-__device__ __forceinline__ void wave_max_slot_f(unsigned* slot, float f) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) f = fmaxf(f, __shfl_xor(f, o));
-    if ((threadIdx.x & 63) == 0) atomicMax(slot, __float_as_uint(f));
-}
 // workgroup max of m (all threads call it; red: >= 8 doubles of free LDS); returned to every thread
 __device__ __forceinline__ double block_max(double m, double* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o));
+    m = wave_fmax(m);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
     __syncthreads();
@@ -131,8 +116,8 @@ __global__ void __launch_bounds__(256) k_zstart(const StartArgs args) {
     const double m = block_max(fabs(s), red);
     if (threadIdx.x == 0) atomicMax(p.eword, exp_word(m));
     const unsigned slot = unsigned(blockIdx.x) % unsigned(kCmaxSlots);
-    wave_max_slot(p.cx + slot, mx);
-    wave_max_slot(p.cy + slot, my);
+    wave_max_atomic(p.cx + slot, fp64_max_as_float(mx));
+    wave_max_atomic(p.cy + slot, fp64_max_as_float(my));
 }
 
 // ------------------------------------------------------------------------------------------------ step
@@ -493,8 +478,8 @@ __device__ __forceinline__ void zstep_unit(const StepEnd& p, const int i, const 
         }
     }
     const unsigned slot = unsigned(unit) % unsigned(kCmaxSlots);
-    wave_max_slot_f(p.cx + slot, vmx);
-    wave_max_slot_f(p.cy + slot, vmy);
+    wave_max_atomic(p.cx + slot, vmx);
+    wave_max_atomic(p.cy + slot, vmy);
     XRS_ZIP_STAMP(4)
 }
 
@@ -585,19 +570,16 @@ __global__ void __launch_bounds__(256) k_zfinish(const TE* __restrict__ E, const
     if (blockIdx.x < kPair) {
         double s = 0.0;
         for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += kPair * 256) s = fma(double(E[i]), double(F[i]), s);
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+        s = block_sum_t0<Order::pairwise4>(s, red);
+        if (threadIdx.x == 0) partial[blockIdx.x] = s;
         return;
     }
     const int c = int(blockIdx.x) - kPair;
     const unsigned* w = slots + size_t(c) * kCmaxSlots;
     unsigned m = 0u;
     for (int i = threadIdx.x; i < kCmaxSlots; i += 256) m = max(m, w[i]);
-    for (int o = 32; o > 0; o >>= 1) m = max(m, unsigned(__shfl_xor(int(m), o)));
-    if ((threadIdx.x & 63) == 0) redu[threadIdx.x >> 6] = m;
-    __syncthreads();
+    m = wave_max(m);
+    wave_partials(m, redu);
     if (threadIdx.x == 0) cmax_out[c] = max(max(redu[0], redu[1]), max(redu[2], redu[3]));
 }
 
