@@ -196,6 +196,29 @@ int xrs_sym_tridiag(xrs_handle_t handle, double* d, double* e, const double* A, 
  *  used: compute the vectors another way (the rounds fall back to their Jacobi / reference routes). Deterministic:
  *  the same input gives the same bits. Synchronises. */
 int xrs_sym_eig_top(xrs_handle_t handle, double* lam, double* Ut, int* status, const double* A, size_t n, size_t kk);
+/** The batched Cholesky family of the TT rounds behind one entry point, exposed for its tests: `count` jobs
+ *  A[i] + shift[i] tr(A[i]) I = L[i] L[i]^T, Z[i] = L[i]^{-1} (A, L, Z: host arrays of device pointers to n[i] x n[i]
+ *  row-major matrices; only the lower triangle of A[i] is read, A[i] is left untouched; L[i] null: a status-only
+ *  certificate, which writes nothing else; Z[i] null: no inverse). L and Z of a job with n <= 256 have exact zeros
+ *  above the diagonal.
+ *  mode 0: the front end in one call (any n); mode 1: its two-call form, factorisations then the deferred inverses
+ *  on the same stream (bit-identical to mode 0); mode 2: the kernels' own batch tables without the front end
+ *  (count <= 48, n <= 512, the 32-wide kernel above 256, which needs L[i]), then the inverses of the jobs with Z.
+ *  status (host, count ints): 0, or 1 + the first column of the whole matrix whose pivot is not in (0, 1e300), i.e.
+ *  the first leading minor that is not positive definite. raw (host, raw_len ints, may be NULL): the front
+ *  end's own status words, all zero for a job that succeeded: modes 0 and 1 one word per job with n <= 256 in job
+ *  order, then two per job of 257..512 (per 64 such jobs the first words, then the second ones), then one per
+ *  256-block of the larger ones; mode 2 one per job. raw_len must be that count. Synchronises once. */
+int xrs_chol_batch(xrs_handle_t handle, size_t count, const double* const* A, double* const* L, double* const* Z,
+                   const int* n, const double* shift, int mode, int* status, int* raw, size_t raw_len);
+/** One single-workgroup Cholesky A + shift_rel tr(A) I = L L^T (n <= 512; lower triangle of A read, L with exact
+ *  zeros above the diagonal, A and L distinct n x n device matrices) and, with nvec > 0, the triangular solve
+ *  X = L^{-1} Y on its diagonal-block inverses; exposed for their tests. cols != 0: the right-hand sides are
+ *  the nvec columns of Y (n x nvec, row stride ldy) and X (row stride ldx); cols == 0: the nvec rows of Y
+ *  (nvec x n, ldy) and X (ldx). *status (host): 0 or 1 + the first failing column; *trace (host): tr(A) as the
+ *  kernel summed it. Synchronises. */
+int xrs_potrf_solve(xrs_handle_t handle, double* L, const double* A, size_t n, double shift_rel, int* status,
+                    double* trace, int cols, const double* Y, size_t ldy, double* X, size_t ldx, size_t nvec);
 
 /* ---------------------------------------------------------------- TT hot path (ttNetwork.cpp) */
 /* A TT of order d is passed as d device core pointers; core k has dims (r[k], n[k], r[k+1]),

@@ -60,6 +60,10 @@ SIGNATURES = {
     "xrs_svd_rows_vt": (C.c_int, [_DP, _DP, _DP, C.POINTER(C.c_int), _DP, _SZ, _SZ, C.c_int]),
     "xrs_sym_eig_top": (C.c_int, [_DP, _DP, _DP, C.POINTER(C.c_int), _DP, _SZ, _SZ]),
     "xrs_sym_tridiag": (C.c_int, [_DP, _DP, _DP, _DP, _SZ]),
+    "xrs_chol_batch": (C.c_int, [_DP, _SZ, C.POINTER(_DP), C.POINTER(_DP), C.POINTER(_DP), C.POINTER(C.c_int),
+                                 C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _SZ]),
+    "xrs_potrf_solve": (C.c_int, [_DP, _DP, _DP, _SZ, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_int,
+                                  _DP, _SZ, _DP, _SZ, _SZ]),
     "xrs_tt_entrywise_product": (C.c_int, [_DP, _SZ, C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(_DP), C.POINTER(_SZ), C.POINTER(_DP),
                                            C.c_double, C.POINTER(_DP)]),
     "xrs_tt_entrywise_square": (C.c_int, [_DP, _SZ, C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(_DP), C.c_double, C.POINTER(_DP),
@@ -403,6 +407,33 @@ class Handle:
         d, e = self.empty((n,)), self.empty((n,))
         _check("xrs_sym_tridiag", self.lib.xrs_sym_tridiag(self.h, _DP(d.ptr), _DP(e.ptr), _DP(A.ptr), n))
         return d.numpy(), e.numpy()[: n - 1]
+
+    @staticmethod
+    def chol_status_words(ns: Sequence[int]) -> int:
+        """Status words the batched Cholesky front end writes for jobs of these orders (chol_status_count)."""
+        return sum(1 if n <= 256 else 2 if n <= 512 else (n + 255) // 256 for n in ns)
+
+    def chol_batch(self, A: Sequence[int], L: Sequence[int], Z: Sequence[int], n: Sequence[int], shift: Sequence[float],
+                   mode: int = 0):
+        """xrs_chol_batch over raw device pointers (0 = null: L for a certificate, Z for no inverse); exposed for the
+        tests of the batched Cholesky family. Returns (status per job, the front end's raw status words)."""
+        cnt = len(A)
+        words = cnt if mode == 2 else self.chol_status_words(n)
+        tab = lambda xs: (_DP * max(1, cnt))(*[_DP(int(x) or None) for x in xs])  # noqa: E731
+        ns = (C.c_int * max(1, cnt))(*[int(v) for v in n])
+        sh = (C.c_double * max(1, cnt))(*[float(v) for v in shift])
+        st, raw = (C.c_int * max(1, cnt))(), (C.c_int * max(1, words))()
+        _check("xrs_chol_batch", self.lib.xrs_chol_batch(self.h, cnt, tab(A), tab(L), tab(Z), ns, sh, int(mode), st, raw, words))
+        return list(st[:cnt]), list(raw[:words])
+
+    def potrf_solve(self, L: int, A: int, n: int, shift_rel: float = 0.0, cols: bool = True, Y: int = 0, ldy: int = 0,
+                    X: int = 0, ldx: int = 0, nvec: int = 0):
+        """xrs_potrf_solve over raw device pointers: one potrf of A into L and, with nvec > 0, X = L^{-1} Y by trsm;
+        exposed for their tests. Returns (status, trace)."""
+        st, tr = C.c_int(), C.c_double()
+        _check("xrs_potrf_solve", self.lib.xrs_potrf_solve(self.h, _DP(L), _DP(A), n, float(shift_rel), C.byref(st), C.byref(tr),
+                                                          int(cols), _DP(Y or None), ldy, _DP(X or None), ldx, nvec))
+        return st.value, tr.value
 
     def svd_rows_vt(self, A: "DeviceArray", kernel: int = 0):
         """(S, Vt, sweeps) of the rows of A (p <= q <= 512) by one-sided Jacobi (xrs_svd_rows_vt)."""

@@ -293,4 +293,95 @@ void chol_enqueue(xrs_handle_t h, const std::vector<CholJob>& jobs, int* status,
     chol_enqueue_inverses(h, later);
 }
 
+namespace {
+
+// 1 + first failing column of the whole matrix from the front end's words of every job (the layout above)
+void decode_status(const std::vector<CholJob>& jobs, const std::vector<int>& raw, int* status) {
+    int ns = 0, nb = 0;
+    for (const CholJob& j : jobs) {
+        ns += j.n <= 256;
+        nb += j.n > 256 && j.n <= 512;
+    }
+    int is = 0, ib = 0, slot = ns + 2 * nb;
+    for (size_t i = 0; i < jobs.size(); ++i) {
+        const int n = jobs[i].n;
+        if (n <= 256) {
+            status[i] = raw[size_t(is++)];
+        } else if (n <= 512) {
+            const int b0 = ib / kBigMax * kBigMax, part = std::min(kBigMax, nb - b0);   // this job's chunk of factor_big
+            const int w1 = raw[size_t(ns + 2 * b0 + (ib - b0))], w2 = raw[size_t(ns + 2 * b0 + part + (ib - b0))];
+            status[i] = w1 ? w1 : (w2 ? 256 + w2 : 0);
+            ++ib;
+        } else {
+            status[i] = 0;
+            const int blocks = chol_full_blocks(size_t(n));
+            for (int b = 0; b < blocks && !status[i]; ++b)
+                if (raw[size_t(slot + b)]) status[i] = 256 * b + raw[size_t(slot + b)];
+            slot += blocks;
+        }
+    }
+}
+
+}  // namespace
+
 }  // namespace xrs
+
+extern "C" int xrs_chol_batch(xrs_handle_t h, size_t count, const double* const* A, double* const* L, double* const* Z,
+                              const int* n, const double* shift, int mode, int* status, int* raw, size_t raw_len) {
+    using namespace xrs;
+    return guarded([&] {
+        XRS_REQUIRE(h && (count == 0 || (A && L && Z && n && shift && status)), "null argument");
+        XRS_REQUIRE(mode >= 0 && mode <= 2, "xrs_chol_batch: mode is 0, 1 or 2");
+        if (count == 0) return;
+        std::vector<CholJob> jobs;
+        for (size_t i = 0; i < count; ++i) {
+            XRS_REQUIRE(A[i] != nullptr && n[i] >= 1, "xrs_chol_batch: empty job");
+            XRS_REQUIRE(L[i] != nullptr || Z[i] == nullptr, "xrs_chol_batch: Z without L");
+            XRS_REQUIRE(L[i] != A[i] && (Z[i] == nullptr || (Z[i] != A[i] && Z[i] != L[i])), "xrs_chol_batch: aliased job");
+            jobs.push_back(CholJob{A[i], n[i], L[i], Z[i], shift[i]});
+        }
+        const int words = mode == 2 ? int(count) : chol_status_count(jobs);
+        XRS_REQUIRE(raw == nullptr || raw_len == size_t(words), "xrs_chol_batch: raw_len is not the status word count");
+        fence_readers(h);
+        DevBuf st(h, size_t(words) * sizeof(int));
+        // (every word is written by its job: a word a launch missed reads back as -1, not as a success)
+        XRS_HIP(hipMemsetAsync(st.p, 0xFF, size_t(words) * sizeof(int), h->stream));
+        std::vector<DevBuf> keep;
+        if (mode == 0) {
+            chol_enqueue(h, jobs, st.as<int>(), keep);
+        } else if (mode == 1) {
+            CholInverses later;
+            chol_enqueue_factors(h, jobs, st.as<int>(), keep, later);
+            chol_enqueue_inverses(h, later);
+        } else {
+            XRS_REQUIRE(count <= size_t(kPotrfBatchMax), "xrs_chol_batch: mode 2 holds at most 48 jobs");
+            PotrfBatch pb{};
+            TrinvBatch tb{};
+            int nz = 0;
+            for (size_t i = 0; i < count; ++i) {
+                XRS_REQUIRE(n[i] <= kSmallMax, "xrs_chol_batch: mode 2 needs n <= 512");
+                keep.emplace_back(h, dinv_elems(n[i]) * 8);
+                pb.src[i] = A[i];
+                pb.G[i] = L[i];
+                pb.Dinv[i] = keep.back().d();
+                pb.shift[i] = shift[i];
+                pb.n[i] = n[i];
+                if (Z[i]) {
+                    tb.L[nz] = L[i];
+                    tb.Dinv[nz] = keep.back().d();
+                    tb.X[nz] = Z[i];
+                    tb.n[nz] = n[i];
+                    ++nz;
+                }
+            }
+            pb.status = st.as<int>();
+            potrf_batched(h, pb, int(count));
+            trinv_batched(h, tb, nz);
+        }
+        std::vector<int> words_host(size_t(words), 0);
+        read_status(h, st.as<int>(), words, words_host.data());
+        if (mode == 2) std::copy(words_host.begin(), words_host.end(), status);
+        else decode_status(jobs, words_host, status);
+        if (raw) std::copy(words_host.begin(), words_host.end(), raw);
+    });
+}

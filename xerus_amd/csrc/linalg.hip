@@ -589,4 +589,22 @@ int xrs_svd_rows_vt(xrs_handle_t h, double* S, double* Vt, int* sweeps, const do
     });
 }
 
+int xrs_potrf_solve(xrs_handle_t h, double* L, const double* A, size_t n, double shift_rel, int* status, double* trace,
+                    int cols, const double* Y, size_t ldy, double* X, size_t ldx, size_t nvec) {
+    return guarded([&] {
+        XRS_REQUIRE(h && L && A && status && trace && L != A, "null or aliased argument");
+        XRS_REQUIRE(n >= 1 && n <= size_t(kSmallMax), "xrs_potrf_solve: need 1 <= n <= 512");
+        XRS_REQUIRE(nvec == 0 || (Y && X && X != Y && nvec < (1u << 24)), "xrs_potrf_solve: null, aliased or oversized right-hand sides");
+        XRS_REQUIRE(nvec == 0 || (cols ? (ldy >= nvec && ldx >= nvec) : (ldy >= n && ldx >= n)),
+                    "xrs_potrf_solve: leading dimension too small");
+        fence_readers(h);
+        DevBuf Dinv(h, dinv_elems(int(n)) * 8), st(h, 64), info(h, 64);
+        XRS_HIP(hipMemcpyAsync(L, A, n * n * 8, hipMemcpyDeviceToDevice, h->stream));
+        potrf(h, L, int(n), shift_rel, Dinv.d(), st.as<int>(), info.d());
+        trsm(h, cols != 0, L, Dinv.d(), int(n), Y, ldy, X, ldx, int(nvec));
+        XRS_HIP(hipMemcpyAsync(trace, info.d(), 8, hipMemcpyDeviceToHost, h->stream));
+        read_status(h, st.as<int>(), 1, status);
+    });
+}
+
 }  // extern "C"

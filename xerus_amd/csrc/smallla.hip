@@ -425,7 +425,9 @@ __device__ __forceinline__ void potrf_rr_body(double* __restrict__ G, int n, dou
         // all 4*PR_SLOTS loads are in flight together); padding / shift fixed up below
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const int row = min(max(16 * i + lg + 4 * q, 0), n - 1), col = min(max(16 * k + lr, 0), n - 1);
+            // lower triangle read: an element above the diagonal (diagonal tiles only) comes from its mirror
+            const int er = min(max(16 * i + lg + 4 * q, 0), n - 1), ec = min(max(16 * k + lr, 0), n - 1);
+            const int row = max(er, ec), col = min(er, ec);
             acc[s][q] = S[size_t(row) * n + col];
         }
     }
@@ -612,7 +614,9 @@ __device__ __forceinline__ void potrf_la_body(double* __restrict__ G, int n, dou
         tk[s] = k;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const int row = min(max(16 * i + lg + 4 * q, 0), n - 1), col = min(max(16 * k + lr, 0), n - 1);
+            // lower triangle read: an element above the diagonal (diagonal tiles only) comes from its mirror
+            const int er = min(max(16 * i + lg + 4 * q, 0), n - 1), ec = min(max(16 * k + lr, 0), n - 1);
+            const int row = max(er, ec), col = min(er, ec);
             acc[s][q] = S[size_t(row) * n + col];
         }
     }

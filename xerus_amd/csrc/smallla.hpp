@@ -10,8 +10,8 @@ namespace xrs {
 constexpr int kSmallMax = 512;  // largest n handled by the single-workgroup kernels
 
 // G (n x n) := L with G + shift_rel*trace(G)*I = L L^T (lower, upper zeroed); Dinv: n x 32 inverses of the
-// diagonal blocks. *status_dev = 0 on success, else 1 + first failing column; info_dev[0] = trace(G)
-// (may be null). Enqueued only.
+// diagonal blocks. Only the lower triangle of the input is read (both kernels, the batched forms included).
+// *status_dev = 0 on success, else 1 + first failing column; info_dev[0] = trace(G) (may be null). Enqueued only.
 void potrf(xrs_handle_t h, double* G, int n, double shift_rel, double* Dinv, int* status_dev, double* info_dev = nullptr);
 // Batch of independent Cholesky factorisations (n <= 256 each), one workgroup per matrix, each with its
 // own relative diagonal shift; status[i] as for potrf. Dinv[i] needs ceil(n_i/16)*256 doubles.
