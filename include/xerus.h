@@ -19,6 +19,7 @@
 #include "xerus/algorithms/uqAdf.h"
 #include "xerus/algorithms/largestEntry.h"
 #include "xerus/algorithms/randomSVD.h"
+#include "xerus/algorithms/randomizedRounding.h"
 #include "xerus/algorithms/decompositionAls.h"
 
 namespace xerus {

@@ -117,6 +117,17 @@ int xrs_gemm_forms(xrs_handle_t handle, size_t count, double* const* C, size_t M
                    const double* const* A, size_t lda, int transA, size_t K,
                    const double* const* B, size_t ldb, int transB, int sym, int tri);
 
+/** Extension (no reference counterpart): the summed GEMM C (M x N, ldc = N) = alpha * sum_j A[j] (M x K[j], row
+ *  stride lda[j]) * B[j] (K[j] x N, row stride ldb[j]), j < count, the operands of every term in their own
+ *  allocations (A, B: host arrays of device pointers; lda, K, ldb: host arrays). Segments are ragged; K[j] = 0 is
+ *  legal, contributes nothing and its pointers are not looked at (they may be null). count >= 1 without an upper
+ *  limit. No transposed forms. C must not alias an operand (XRS_EINVAL). The split over the concatenated K is a
+ *  function of (M, N, count, K) only and is summed in a fixed order: the same call gives the same bits. Enqueued
+ *  only. The product behind the randomized rounding of TT sums (xrs_tt_round_randomized). */
+int xrs_gemm_ksum(xrs_handle_t handle, double* C, size_t M, size_t N, double alpha, size_t count,
+                  const double* const* A, const size_t* lda, const size_t* K,
+                  const double* const* B, const size_t* ldb);
+
 /** fp32 form of xrs_gemm on the fp32 matrix cores (v_mfma_f32_16x16x4_f32, 157.3 TF/s peak): C = alpha *
  *  op(A) * op(B), float operands and result, row-major, ldc = N; argument order, ld rules and aliasing as
  *  xrs_gemm. The reduced-precision variant of blasWrapper::matrix_matrix_product (blasLapackWrapper.cpp:
@@ -454,6 +465,19 @@ int xrs_sketch_gaussian(xrs_handle_t handle, double* Y, size_t s, const double* 
                         uint32_t stream, int route);
 /** The route the handle's last xrs_sketch_gaussian took (XRS_SKETCH_*); 0 before the first. */
 int xrs_sketch_last_route(xrs_handle_t handle);
+
+/** Randomize-then-orthogonalize rounding of the TT sum sum_j coef[j] Y^(j) (Al Daas, Ballard, Cazeaux, Hallman,
+ *  Miedlar, Pasha, Reid, Saibaba: "Randomized algorithms for rounding in the tensor-train format", SISC 2023;
+ *  include/xerus/algorithms/randomizedRounding.h has the recursion). `count` terms over the same mode sizes n[0..d-1];
+ *  r[j]: the d + 1 ranks of term j (boundary ranks 1), cores[j][k]: its core (r[j][k], n[k], r[j][k+1]) row-major;
+ *  ell: the d - 1 sketch ranks (>= 1; unused for d = 1). The sketch rank of edge k is capped, left to right, by the
+ *  product of the modes on either side, by sum_j r[j][k] and by (capped rank of edge k - 1) * n[k-1]; r_out (d + 1
+ *  entries) receives the capped ranks. The random TT is drawn from G(seed, stream = k), k = 1 .. d-1. out receives
+ *  d new cores from the handle's pool (the caller frees them with xrs_free; none is left allocated on failure):
+ *  cores 0 .. d-2 are left-orthonormal, the core sits at d - 1. The block-diagonal sum is never formed. */
+int xrs_tt_round_randomized(xrs_handle_t handle, size_t d, const size_t* n, size_t count, const size_t* const* r,
+                            const double* const* const* cores, const double* coef, const size_t* ell, uint64_t seed,
+                            double** out, size_t* r_out);
 
 /* ---------------------------------------------------------------- matrix-free ALS local problem (als.cpp:383-400) */
 /* The local operator M of a one-site ALS step, applied through its two environments and the operator core instead

@@ -47,6 +47,10 @@ SIGNATURES = {
                                    C.POINTER(_DP), _SZ, C.c_int]),
     "xrs_gemm_forms": (C.c_int, [_DP, _SZ, C.POINTER(_DP), _SZ, _SZ, C.c_double, C.POINTER(_DP), _SZ, C.c_int, _SZ,
                                  C.POINTER(_DP), _SZ, C.c_int, C.c_int, C.c_int]),
+    "xrs_gemm_ksum": (C.c_int, [_DP, _DP, _SZ, _SZ, C.c_double, _SZ, C.POINTER(_DP), C.POINTER(_SZ), C.POINTER(_SZ),
+                                C.POINTER(_DP), C.POINTER(_SZ)]),
+    "xrs_tt_round_randomized": (C.c_int, [_DP, _SZ, C.POINTER(_SZ), _SZ, C.POINTER(C.POINTER(_SZ)), C.POINTER(C.POINTER(_DP)),
+                                          C.POINTER(C.c_double), C.POINTER(_SZ), C.c_uint64, C.POINTER(_DP), C.POINTER(_SZ)]),
     "xrs_permute": (C.c_int, [_DP, _DP, _DP, _SZ, C.POINTER(_SZ), C.POINTER(_SZ)]),
     "xrs_qc": (C.c_int, [_DP, _DP, _DP, C.POINTER(_SZ), _DP, _SZ, _SZ]),
     "xrs_cq": (C.c_int, [_DP, _DP, _DP, C.POINTER(_SZ), _DP, _SZ, _SZ]),
@@ -268,6 +272,46 @@ class Handle:
         tab = lambda xs: (_DP * max(1, cnt))(*[_DP(x.ptr) for x in xs])  # noqa: E731
         _check("xrs_gemm_forms", self.lib.xrs_gemm_forms(self.h, cnt, tab(Cs), M, N, alpha, tab(As), lda, int(transA), K,
                                                         tab(Bs), ldb, int(transB), int(sym), int(tri)))
+
+    def gemm_ksum(self, C_: "DeviceArray", M, N, alpha, As, Bs, Ks=None, ldas=None, ldbs=None):
+        """xrs_gemm_ksum: C_ (M x N) = alpha * sum_j As[j] (M x Ks[j], row stride ldas[j]) @ Bs[j] (Ks[j] x N, row stride
+        ldbs[j]). As / Bs: lists of DeviceArrays (None: a null pointer, legal where Ks[j] = 0). Defaults: Ks[j] and
+        ldas[j] from As[j].shape[1], ldbs[j] = N."""
+        cnt = len(As)
+        if len(Bs) != cnt:
+            raise XrsError("xrs_gemm_ksum", -1, f"{cnt} A operands but {len(Bs)} B operands")
+        Ks = [a.shape[1] for a in As] if Ks is None else list(Ks)
+        ldas = [max(1, k) for k in Ks] if ldas is None else list(ldas)
+        ldbs = [N] * cnt if ldbs is None else list(ldbs)
+        if not (len(Ks) == len(ldas) == len(ldbs) == cnt) or min([M, N, *Ks, *ldas, *ldbs], default=0) < 0:
+            raise XrsError("xrs_gemm_ksum", -1, "Ks, ldas and ldbs need one non-negative entry per operand")
+        tab = lambda xs: (_DP * max(1, cnt))(*[_DP(x.ptr if x is not None else 0) for x in xs])  # noqa: E731
+        sz = lambda xs: (_SZ * max(1, cnt))(*[int(v) for v in xs])  # noqa: E731
+        _check("xrs_gemm_ksum", self.lib.xrs_gemm_ksum(self.h, _DP(C_.ptr), M, N, float(alpha), cnt, tab(As), sz(ldas), sz(Ks),
+                                                      tab(Bs), sz(ldbs)))
+
+    def tt_round_randomized(self, terms, coef, ell, seed: int) -> "TTDevice":
+        """xrs_tt_round_randomized: the rank-ell sketch of sum_j coef[j] terms[j] (TTDevices over the same dimensions) as
+        a new TTDevice with the capped ranks, cores 0 .. d-2 left-orthonormal, the core at d - 1. No closing round."""
+        seed, _ = self._seed_stream("xrs_tt_round_randomized", seed, 0)
+        cnt = len(terms)
+        if cnt == 0 or len(coef) != cnt:
+            raise XrsError("xrs_tt_round_randomized", -1, f"{cnt} terms with {len(coef)} coefficients")
+        dims = terms[0].dims
+        d = len(dims)
+        if any(t.dims != dims for t in terms):
+            raise XrsError("xrs_tt_round_randomized", -1, "the terms have different dimensions")
+        if len(ell) != d - 1 or any(int(v) < 0 for v in ell):
+            raise XrsError("xrs_tt_round_randomized", -1, f"{d - 1} non-negative sketch ranks are needed, got {list(ell)}")
+        rs = [_arr(t.r) for t in terms]
+        cs = [(_DP * d)(*t.ptrs) for t in terms]
+        rtab = (C.POINTER(_SZ) * cnt)(*[C.cast(r, C.POINTER(_SZ)) for r in rs])
+        ctab = (C.POINTER(_DP) * cnt)(*[C.cast(c, C.POINTER(_DP)) for c in cs])
+        cf = (C.c_double * cnt)(*[float(c) for c in coef])
+        out, r_out = (_DP * d)(), (_SZ * (d + 1))()
+        _check("xrs_tt_round_randomized", self.lib.xrs_tt_round_randomized(self.h, d, _arr(dims), cnt, rtab, ctab, cf,
+                                                                          _arr(list(ell) + [1]), seed, out, r_out))
+        return TTDevice(self, dims, list(r_out), [p or 0 for p in out], canonicalized=True, core_position=d - 1)
 
     def tangent_to_tt(self, n, r, Us, Vs, add_base: bool):
         """xrs_tt_tangent_to_tt: the rank-2r block cores of a tangent vector (components Vs at the base Us, both

@@ -376,6 +376,22 @@ PYBIND11_MODULE(xerus, m) {
           py::arg("accuracy"), py::arg("lowerBound") = 0.0);
     m.def("randomTTSVD", &randomTTSVD, py::arg("x"), py::arg("ranks"), py::arg("oversampling"),
           "TT approximation from Gaussian sketches (algorithms/randomSVD.h); seeded by one word of the thread's engine");
+    m.def("sum_rounded",
+          py::overload_cast<const std::vector<TTTensor>&, const std::vector<value_t>&, const std::vector<size_t>&,
+                            const std::vector<size_t>&>(&sum_rounded),
+          py::arg("terms"), py::arg("coefficients"), py::arg("ranks"), py::arg("oversampling"),
+          "sum_j coefficients[j] terms[j] rounded to ranks by randomized sketching, the sum never formed "
+          "(algorithms/randomizedRounding.h); seeded by one word of the thread's engine");
+    m.def("sum_rounded",
+          py::overload_cast<const std::vector<TTOperator>&, const std::vector<value_t>&, const std::vector<size_t>&,
+                            const std::vector<size_t>&>(&sum_rounded),
+          py::arg("terms"), py::arg("coefficients"), py::arg("ranks"), py::arg("oversampling"));
+    m.def("round_randomized",
+          py::overload_cast<const TTTensor&, const std::vector<size_t>&, const std::vector<size_t>&>(&round_randomized),
+          py::arg("x"), py::arg("ranks"), py::arg("oversampling"), "a randomized round(ranks) of x (algorithms/randomizedRounding.h)");
+    m.def("round_randomized",
+          py::overload_cast<const TTOperator&, const std::vector<size_t>&, const std::vector<size_t>&>(&round_randomized),
+          py::arg("x"), py::arg("ranks"), py::arg("oversampling"));
     m.def("decomposition_als", &decomposition_als, py::arg("x"), py::arg("b"), py::arg("epsilon") = EPSILON,
           py::arg("maxIterations") = size_t(1000), "fits the TT x (in place) to the dense tensor b (algorithms/decompositionAls.h)");
     m.def("dyadic_product", py::overload_cast<const TTTensor&, const TTTensor&>(&dyadic_product));
