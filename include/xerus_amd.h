@@ -182,8 +182,21 @@ int xrs_solve(xrs_handle_t handle, double* X, const double* A, size_t m, size_t 
 /** Minimum-norm least-squares solution of A X = B (replaces blasWrapper::solve_least_squares / dgelsd,
  *  blasLapackWrapper.cpp:647-721): X = V S^+ U^T B, singular values <= EPSILON * sigma_max dropped
  *  (min(m, n) <= 512); above, a shifted-CholeskyQR3 QR / LQ solve for full-rank A (rank-deficient A of
- *  that size: XRS_ENUMERIC). */
+ *  that size: XRS_ENUMERIC; refused is every A whose second Cholesky pass meets a pivot below
+ *  16 (m + n) u, which is sigma_min / |A|_F below about 5e-11 at 700 x 560). */
 int xrs_solve_least_squares(xrs_handle_t handle, double* X, const double* A, size_t m, size_t n, const double* B, size_t p);
+/** Which route the handle's last dense solve (xrs_solve, xrs_solve_least_squares, Tensor::solve) took; 0 before
+ *  the first. XRS_SOLVE_CHOLESKY: the blocked Cholesky factored and solved; XRS_SOLVE_SVD: the SVD pseudo-inverse
+ *  with its rank cut (min(m, n) <= 512); XRS_SOLVE_QR: the shifted-CholeskyQR3 QR / LQ solve (min(m, n) > 512; also
+ *  reported when that route refuses a rank-deficient system with XRS_ENUMERIC). XRS_SOLVE_CHOL_FAILED is a flag
+ *  or-ed onto _SVD / _QR: the dispatch chose Cholesky (symmetric, positive diagonal), a diagonal block was not
+ *  positive definite, and the general route solved the system instead. Recorded on the host from values the
+ *  dispatch has already read back: no launch, no synchronisation. */
+#define XRS_SOLVE_CHOLESKY 1
+#define XRS_SOLVE_SVD 2
+#define XRS_SOLVE_QR 3
+#define XRS_SOLVE_CHOL_FAILED 4
+int xrs_solve_last_path(xrs_handle_t handle);
 /** Singular values and right singular vectors of the rows of A (p x q, p <= q <= 1024; kernel 1: p <= 512) by one-sided
  *  Jacobi -- the SVD step of the truncating TT round (TTNetwork::round's per-edge svd,
  *  ttNetwork.cpp:644-665, without U). S: p descending; Vt: p x q, orthonormal rows for S > 0.

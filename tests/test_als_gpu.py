@@ -153,6 +153,7 @@ def test_solve_spd_blocked_cholesky(xe, n, p):
     X = xe.solve(_tensor(xe, M), _tensor(xe, B), 1 if p > 1 else 0).to_ndarray()   # extraDegree: the rhs columns
     assert X.shape == B.shape
     assert _rel(M @ X, B) <= 1e-12
+    assert xe.last_solve_path() == 1   # XRS_SOLVE_CHOLESKY: the blocked Cholesky itself, not its fallback
 
 
 @pytest.mark.parametrize("m,n", [(200, 200), (300, 120), (120, 300)])
@@ -161,9 +162,11 @@ def test_solve_general_and_least_squares(xe, m, n):
     M = rng.standard_normal((m, n))
     B = rng.standard_normal((m, 2))
     X = xe.solve(_tensor(xe, M), _tensor(xe, B), 1).to_ndarray()
+    assert xe.last_solve_path() == 2   # XRS_SOLVE_SVD
     want = np.linalg.lstsq(M, B, rcond=None)[0]
     assert _rel(X, want) <= 1e-10
     X2 = xe.solve_least_squares(_tensor(xe, M), _tensor(xe, B), 1).to_ndarray()
+    assert xe.last_solve_path() == 2
     assert _rel(X2, want) <= 1e-10
 
 
@@ -176,8 +179,10 @@ def test_solve_general_above_512(xe, m, n):
     B = rng.standard_normal((m, 3))
     want = np.linalg.lstsq(M, B, rcond=None)[0]
     X = xe.solve(_tensor(xe, M), _tensor(xe, B), 1).to_ndarray()
+    assert xe.last_solve_path() == 3   # XRS_SOLVE_QR
     assert _rel(X, want) <= 1e-9
     X2 = xe.solve_least_squares(_tensor(xe, M), _tensor(xe, B), 1).to_ndarray()
+    assert xe.last_solve_path() == 3
     assert _rel(X2, want) <= 1e-9
 
 

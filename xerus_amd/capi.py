@@ -61,6 +61,7 @@ SIGNATURES = {
     "xrs_svd_batched_fits": (C.c_int, [_SZ, _SZ]),
     "xrs_solve": (C.c_int, [_DP, _DP, _DP, _SZ, _SZ, _DP, _SZ]),
     "xrs_solve_least_squares": (C.c_int, [_DP, _DP, _DP, _SZ, _SZ, _DP, _SZ]),
+    "xrs_solve_last_path": (C.c_int, [_DP]),
     "xrs_svd_rows_vt": (C.c_int, [_DP, _DP, _DP, C.POINTER(C.c_int), _DP, _SZ, _SZ, C.c_int]),
     "xrs_sym_eig_top": (C.c_int, [_DP, _DP, _DP, C.POINTER(C.c_int), _DP, _SZ, _SZ]),
     "xrs_sym_tridiag": (C.c_int, [_DP, _DP, _DP, _DP, _SZ]),
@@ -133,6 +134,8 @@ KFAM_GEMM, KFAM_PERMUTE, KFAM_QR, KFAM_SVD, KFAM_ELEMWISE, KFAM_SPLITK = 1, 2, 4
 ROUND_PATHS = {0: None, 1: "chain", 2: "truncate", 3: "reference", 4: "general"}
 SKETCH_AUTO, SKETCH_FUSED, SKETCH_MATERIALISED = 0, 1, 2
 SKETCH_ROUTES = {0: None, 1: "fused", 2: "materialised"}
+XRS_ENUMERIC = 1
+SOLVE_PATHS = {0: None, 1: "cholesky", 2: "svd", 3: "qr", 6: "cholesky_failed_svd", 7: "cholesky_failed_qr"}
 
 _lib = None
 
@@ -437,6 +440,10 @@ class Handle:
         fn = "xrs_solve_least_squares" if least_squares else "xrs_solve"
         _check(fn, getattr(self.lib, fn)(self.h, _DP(X.ptr), _DP(A.ptr), m, n, _DP(B.ptr), p))
         return X
+
+    def solve_last_path(self) -> str | None:
+        """"cholesky" / "svd" / "qr" / "cholesky_failed_svd" / "cholesky_failed_qr": the route of this handle's last solve."""
+        return SOLVE_PATHS[self.lib.xrs_solve_last_path(self.h)]
 
     def sym_eig_top(self, A: "DeviceArray", kk: int):
         """(lam, Ut, status): the kk largest eigenpairs of the symmetric A (n <= 128), xrs_sym_eig_top."""

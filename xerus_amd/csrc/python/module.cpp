@@ -63,6 +63,8 @@ PYBIND11_MODULE(xerus, m) {
           "the hipStream_t of the calling thread's handle as an integer (for timing with HIP events)");
     m.def("last_round_path", [] { return xrs_tt_last_round_path(gpu::handle()); },
           "algorithm of the calling thread's last TT round: 1 chain, 2 certified truncation, 3 reference sweeps, 4 general");
+    m.def("last_solve_path", [] { return xrs_solve_last_path(gpu::handle()); },
+          "route of the calling thread's last dense solve: 1 Cholesky, 2 SVD, 3 QR / LQ; + 4: after a refused Cholesky");
     m.def("seed", [](uint64 _s) {
         misc::randomEngine.seed(_s);
         misc::defaultNormalDistribution.reset();

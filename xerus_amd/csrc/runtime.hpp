@@ -109,6 +109,8 @@ struct xrs_handle_s {
     int last_round_path = 0;
     // route of the last xrs_sketch_gaussian (XRS_SKETCH_*)
     int last_sketch_route = 0;
+    // route of the last dense solve (XRS_SOLVE_*, _CHOL_FAILED or-ed on after a refused Cholesky)
+    int last_solve_path = 0;
     // asynchronous TT inner product (xrs_tt_dot_async): enqueued by a worker thread on a child handle
     // whose streams are side streams 1 and 2 of this one (forked at ev_dot from the main stream), so the
     // caller's thread goes on enqueueing the next work at once; while `reader_pending`, releases of the

@@ -196,16 +196,34 @@ void chol_solve(xrs_handle_t h, const double* L, const std::vector<DevBuf>& Z, s
 // explicit inverses of its three Cholesky factors, so the triangular solves are GEMMs:
 //   m >= n: A = Q R, R = L3^T L2^T L1^T       -> X = R^{-1} Q^T B = Z1^T Z2^T Z3^T (Q^T B)
 //   m <  n: A = L Q, L = L1 L2 L3             -> X = Q^T L^{-1} B = Q^T Z3 Z2 Z1 B (the minimum-norm solution)
-// Same solution as the reference's dgesv / dgelsd for a matrix of full rank min(m, n) with kappa < 1/u; a
-// numerically rank-deficient system of that size is rejected (XRS_ENUMERIC) instead of getting dgelsd's
-// truncated minimum-norm solution.
-static void qr_solve_big(xrs_handle_t h, double* X, const double* A, size_t m, size_t n, const double* B, size_t p) {
+// Same solution as the reference's dgesv / dgelsd for a matrix of full numerical rank min(m, n); a numerically
+// rank-deficient system of that size is rejected (XRS_ENUMERIC) instead of getting dgelsd's truncated
+// minimum-norm solution. The second factorisation decides: Q1 = A Z1^T has the Gram matrix G2 with the
+// eigenvalues sigma_i^2 / (sigma_i^2 + s), s = s_rel tr(A^T A), whose computed entries carry an error of about
+// (M + N) u, so a pivot of G2 below 16 (M + N) u is rounding noise of either sign. A pivot <= 0 fails potrf; a
+// positive one of that size passes it (an exactly duplicated column of a 700 x 560 matrix passed all three
+// factorisations and returned a solution of norm 3e14 where dgelsd's has norm 3) and is refused by k_pivot_floor. That bounds the route to sigma_min / |A|_F above about
+// sqrt(16 (M + N) u s_rel) (5e-11 at 700 x 560), not to kappa < 1 / u.
+namespace {
+// flag |= 1 if a pivot 1 / Z_ii^2 of the factorisation with the inverse factor Z is not above tol
+__global__ void __launch_bounds__(256) k_pivot_floor(const double* __restrict__ Z, size_t n, double tol, int* __restrict__ flag) {
+    bool bad = false;
+    for (size_t i = size_t(blockIdx.x) * 256 + threadIdx.x; i < n; i += size_t(gridDim.x) * 256) {
+        const double z = Z[i * n + i];
+        if (!(z * z * tol < 1.0)) bad = true;
+    }
+    if (bad) __hip_atomic_fetch_or(flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+}  // namespace
+
+static void qr_solve_big(xrs_handle_t h, double* X, const double* A, size_t m, size_t n, const double* B, size_t p, int chol_failed) {
+    h->last_solve_path = XRS_SOLVE_QR | chol_failed;
     const bool wide = m < n;
     const size_t N = wide ? m : n, M = wide ? n : m;
     const int nb = chol_full_blocks(N);
     DevBuf G(h, N * N * 8), Z1(h, N * N * 8), Z2(h, N * N * 8), Z3(h, N * N * 8), Q1(h, m * n * 8), Q2(h, m * n * 8),
-        st(h, size_t(3 * nb) * 4 + 64), Y(h, std::max(M, N) * p * 8), Y2(h, std::max(M, N) * p * 8);
-    XRS_HIP(hipMemsetAsync(st.d(), 0, size_t(3 * nb) * 4, h->stream));
+        st(h, size_t(3 * nb + 1) * 4 + 64), Y(h, std::max(M, N) * p * 8), Y2(h, std::max(M, N) * p * 8);
+    XRS_HIP(hipMemsetAsync(st.d(), 0, size_t(3 * nb + 1) * 4, h->stream));   // (last word: k_pivot_floor)
     auto gram = [&](const double* Xm) {
         if (wide) gemm_sym(h, G.d(), N, 1.0, Xm, n, false, M, Xm, n, true);   // X X^T
         else gemm_sym(h, G.d(), N, 1.0, Xm, n, true, M, Xm, n, false);        // X^T X
@@ -220,13 +238,16 @@ static void qr_solve_big(xrs_handle_t h, double* X, const double* A, size_t m, s
     apply(Z1.d(), A, Q1.d());
     gram(Q1.d());
     chol_full(h, G.d(), N, 0.0, nullptr, Z2.d(), st.as<int>() + nb);
+    hipLaunchKernelGGL(k_pivot_floor, dim3(unsigned((N + 255) / 256)), dim3(256), 0, h->stream, Z2.d(), N,
+                       16.0 * double(M + N) * 1.1102230246251565e-16, st.as<int>() + 3 * nb);
+    check_launch("k_pivot_floor");
     apply(Z2.d(), Q1.d(), Q2.d());
     gram(Q2.d());
     chol_full(h, G.d(), N, 0.0, nullptr, Z3.d(), st.as<int>() + 2 * nb);
     double* Q = Q1.d();   // (Q1 no longer needed)
     apply(Z3.d(), Q2.d(), Q);
-    std::vector<int> sts(size_t(3 * nb));
-    read_status(h, st.as<int>(), 3 * nb, sts.data());
+    std::vector<int> sts(size_t(3 * nb + 1));
+    read_status(h, st.as<int>(), 3 * nb + 1, sts.data());
     for (int v : sts)
         if (v != 0) throw Error{XRS_ENUMERIC, "solve: a numerically rank-deficient system with min(m, n) > 512 is not supported"};
     if (!wide) {
@@ -247,12 +268,14 @@ static void qr_solve_big(xrs_handle_t h, double* X, const double* A, size_t m, s
 // dgelsd residuals on ill-conditioned systems (fullTensor_solve.cxx "solve vs least squares", kappa ~ 1e6:
 // without refinement 4.2e-10 against LAPACK's 2.2e-12 for the indefinite system, 3.7e-10 against 4.4e-11 for
 // least squares).
-void svd_solve(xrs_handle_t h, double* X, const double* A, size_t m, size_t n, const double* B, size_t p) {
+// chol_failed: XRS_SOLVE_CHOL_FAILED when the caller's Cholesky was refused first, else 0 (the route report)
+static void general_solve(xrs_handle_t h, double* X, const double* A, size_t m, size_t n, const double* B, size_t p, int chol_failed) {
     const size_t k = std::min(m, n);
     if (k > size_t(kSmallMax)) {
-        qr_solve_big(h, X, A, m, n, B, p);
+        qr_solve_big(h, X, A, m, n, B, p, chol_failed);
         return;
     }
+    h->last_solve_path = XRS_SOLVE_SVD | chol_failed;
     DevBuf U(h, m * k * 8), S(h, k * 8), Vt(h, k * n * 8), Si(h, k * 8), T(h, k * p * 8), R(h, m * p * 8), D(h, n * p * 8);
     svd(h, A, m, n, U.d(), S.d(), Vt.d());
     hipLaunchKernelGGL(k_inv_cut, dim3(unsigned((k + 255) / 256)), dim3(256), 0, h->stream, S.d(), int(k), 8.0 * kEps, Si.d());
@@ -271,6 +294,10 @@ void svd_solve(xrs_handle_t h, double* X, const double* A, size_t m, size_t n, c
     }
 }
 
+void svd_solve(xrs_handle_t h, double* X, const double* A, size_t m, size_t n, const double* B, size_t p) {
+    general_solve(h, X, A, m, n, B, p, 0);
+}
+
 void solve_dense(xrs_handle_t h, double* X, const double* A, size_t m, size_t n, const double* B, size_t p) {
     if (m != n) {
         svd_solve(h, X, A, m, n, B, p);
@@ -286,15 +313,18 @@ void solve_dense(xrs_handle_t h, double* X, const double* A, size_t m, size_t n,
     check_launch("k_sym_flags");
     int fl[2] = {0, 0};
     read_status(h, flags.as<int>(), 2, fl);
+    int chol_failed = 0;
     if (!fl[0] && !fl[1]) {
         DevBuf L(h, n * n * 8);
         std::vector<DevBuf> Z;
         if (chol_blocked(h, A, n, L.d(), Z)) {
+            h->last_solve_path = XRS_SOLVE_CHOLESKY;
             chol_solve(h, L.d(), Z, n, B, p, X);
             return;
         }
+        chol_failed = XRS_SOLVE_CHOL_FAILED;
     }
-    svd_solve(h, X, A, m, n, B, p);
+    general_solve(h, X, A, m, n, B, p, chol_failed);
 }
 
 }  // namespace xrs
@@ -320,5 +350,7 @@ int xrs_solve_least_squares(xrs_handle_t h, double* X, const double* A, size_t m
         svd_solve(h, X, A, m, n, B, p);
     });
 }
+
+int xrs_solve_last_path(xrs_handle_t h) { return h ? h->last_solve_path : 0; }
 
 }  // extern "C"
