@@ -87,6 +87,35 @@ def test_qr_rq_above_512(handle, m, n):
     assert np.abs(Q2h @ Q2h.T - np.eye(n)).max() <= 1e-13
 
 
+def graded_above_512(wide):
+    """600 x 513 Gaussian columns (wide: its transpose, seeded apart) scaled geometrically from 1 down to 1e-9."""
+    A = np.random.default_rng(513 + int(wide)).standard_normal((600, 513)) * np.logspace(0, -9, 513)[None, :]
+    return np.ascontiguousarray(A.T) if wide else A
+
+
+@pytest.mark.parametrize("wide", [False, True])
+def test_qr_rq_above_512_ill_conditioned(handle, wide):
+    """Full rank, cond in [1e8, 1e12], Gram order 513: far above what the certifying shift 4 (M + 2N) u passes
+    (cond ~ 1e6 at this size) and far below 1/u, so the blocked CholeskyQR2 fails its certificate and the shifted
+    CholeskyQR3 has to succeed at its own acceptance bar max |Q^T Q - I| <= 64 N u."""
+    A = graded_above_512(wide)
+    N, u = 513, 2.0 ** -53
+    assert 1e8 <= np.linalg.cond(A) <= 1e12
+    if wide:
+        R, Q = handle.rq(handle.array(A))
+        Qh, Rh = Q.numpy(), R.numpy()
+        res, dev = _rel(Rh @ Qh, A), np.abs(Qh @ Qh.T - np.eye(N)).max()
+    else:
+        Q, R = handle.qr(handle.array(A))
+        Qh, Rh = Q.numpy(), R.numpy()
+        res, dev = _rel(Qh @ Rh, A), np.abs(Qh.T @ Qh - np.eye(N)).max()
+    print(f"wide={wide}: residual {res:.3e}, max |QtQ - I| {dev:.3e} (bar {64 * N * u:.3e})")
+    assert dev <= 64 * N * u
+    assert res <= TOL
+    # a product of Cholesky factors (the Householder emulation behind a refused CholeskyQR3 leaves mixed signs)
+    assert np.all(np.diag(Rh) > 0)
+
+
 @pytest.mark.parametrize("m,n", [(8, 5), (5, 8), (64, 64), (128, 128), (30, 200), (200, 30), (1, 5), (5, 1),
                                  (256, 256), (512, 512), (300, 512), (512, 300), (100, 100), (90, 64)])
 def test_svd(handle, ref, m, n):

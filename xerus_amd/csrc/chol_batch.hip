@@ -1,6 +1,6 @@
 // Batched Cholesky front end of the TT rounds (chol_batch.hpp): dispatch of a job list over the three size
 // classes -- n <= 256 (register-resident batched kernels, smallla.hip), 257..512 (2 x 2 blocks of those,
-// below) and above (blocked, solve.hip chol_full) -- with the kernels' argument tables chunked here.
+// below) and above (solve.hip chol_full, the one blocked Cholesky) -- with the kernels' argument tables chunked here.
 #include <algorithm>
 
 #include "reduce_dev.hpp"

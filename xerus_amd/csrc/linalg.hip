@@ -11,18 +11,17 @@
 // still yields an orthonormal Q for any A with kappa < 1/u; exact rank semantics then come from the
 // single-workgroup dgeqp3 emulation applied to the small n x n triangular factor, with the sign of
 // dgeqp3's R_00 taken from A itself (it is -sign(A[0][p]) for the first max-norm column p).
+// The passes, shifts and factor products are cholqr.hpp's, shared with the dense QR solve and the general round.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 
+#include "cholqr.hpp"
 #include "reduce_dev.hpp"
 #include "scratch_map.hpp"
 #include "smallla.hpp"
 
 namespace xrs {
-
-constexpr double kU = 1.1102230246251565e-16;       // unit roundoff 2^-53
-constexpr double kDblEps = 2.220446049250313e-16;   // std::numeric_limits<double>::epsilon()
 
 void transpose(xrs_handle_t h, double* out, const double* in, size_t rows, size_t cols) {
     const size_t dims[2] = {rows, cols};
@@ -89,97 +88,58 @@ static double max_abs_dev_identity(xrs_handle_t h, const double* G, size_t n) {
 // triangular solves become GEMMs with L^{-1}. No Householder last resort at this size: a matrix that
 // fails the verified shifted CholeskyQR3 (kappa >= 1/u) is rejected.
 static OrthResult orthogonalize_big(xrs_handle_t h, const double* A, size_t m, size_t n, bool wide, double* Q, double* RL) {
-    const size_t N = wide ? m : n, M = wide ? n : m;
-    OrthResult res{false, 0.0, false};
+    const cholqr::Shape s{m, n, wide};
+    const size_t N = s.N(), M = s.M();
     const int nb = chol_full_blocks(N);
     DevBuf G(h, N * N * 8), L1(h, N * N * 8), Z1(h, N * N * 8), L2(h, N * N * 8), Z2(h, N * N * 8), L3(h, N * N * 8),
         Z3(h, N * N * 8), T(h, N * N * 8), Q1(h, m * n * 8), Q2(h, m * n * 8), st(h, size_t(3 * nb) * 4 + 64);
-    auto gram = [&](double* out, const double* X) {
-        if (wide) gemm_sym(h, out, N, 1.0, X, n, false, M, X, n, true);   // X X^T
-        else gemm_sym(h, out, N, 1.0, X, n, true, M, X, n, false);        // X^T X
-    };
-    auto apply = [&](const double* Z, const double* X, double* out) {   // tall: X Z^T, wide: Z X
-        if (wide) gemm(h, out, N, n, 1.0, Z, N, false, N, X, n, false);
-        else gemm(h, out, m, N, 1.0, X, n, false, N, Z, N, true);
-    };
-    auto all_zero = [&](int count) {
-        std::vector<int> s(static_cast<size_t>(count));
-        read_status(h, st.as<int>(), count, s.data());
-        for (int v : s)
-            if (v != 0) return false;
-        return true;
-    };
-    const double tau_rel = 4.0 * double(M + 2 * N) * kU;
-    gram(G.d(), A);
-    chol_full(h, G.d(), N, -tau_rel, L1.d(), Z1.d(), st.as<int>());
-    apply(Z1.d(), A, Q1.d());
-    gram(G.d(), Q1.d());
-    chol_full(h, G.d(), N, 0.0, L2.d(), Z2.d(), st.as<int>() + nb);
-    apply(Z2.d(), Q1.d(), Q);
-    if (wide) gemm(h, RL, N, N, 1.0, L1.d(), N, false, N, L2.d(), N, false);   // L = L1 L2
-    else gemm(h, RL, N, N, 1.0, L2.d(), N, true, N, L1.d(), N, true);         // R = L2^T L1^T
-    if (all_zero(2 * nb)) {
-        res.certified = true;
-        res.cert_ratio = std::sqrt(0.5 * tau_rel);
-        return res;
-    }
-    res.robust = true;
-    const double s_rel = 11.0 * (double(M) * N + double(N) * (N + 1)) * kU;
-    gram(G.d(), A);
-    chol_full(h, G.d(), N, s_rel, L1.d(), Z1.d(), st.as<int>());
-    apply(Z1.d(), A, Q1.d());
-    gram(G.d(), Q1.d());
-    chol_full(h, G.d(), N, 0.0, L2.d(), Z2.d(), st.as<int>() + nb);
-    apply(Z2.d(), Q1.d(), Q2.d());
-    gram(G.d(), Q2.d());
-    chol_full(h, G.d(), N, 0.0, L3.d(), Z3.d(), st.as<int>() + 2 * nb);
-    apply(Z3.d(), Q2.d(), Q);
-    if (wide) {   // L = L1 L2 L3
-        gemm(h, T.d(), N, N, 1.0, L1.d(), N, false, N, L2.d(), N, false);
-        gemm(h, RL, N, N, 1.0, T.d(), N, false, N, L3.d(), N, false);
-    } else {      // R = L3^T L2^T L1^T
-        gemm(h, T.d(), N, N, 1.0, L3.d(), N, true, N, L2.d(), N, true);
-        gemm(h, RL, N, N, 1.0, T.d(), N, false, N, L1.d(), N, true);
-    }
-    if (all_zero(3 * nb)) {
-        gram(T.d(), Q);
-        if (max_abs_dev_identity(h, T.d(), N) <= 64.0 * double(N) * kU) return res;
+    int* stv = st.as<int>();
+    const cholqr::Factor f[3] = {{.G = G.d(), .status = stv, .L = L1.d(), .Z = Z1.d()},
+                                 {.G = G.d(), .status = stv + nb, .L = L2.d(), .Z = Z2.d()},
+                                 {.G = G.d(), .status = stv + 2 * nb, .L = L3.d(), .Z = Z3.d()}};
+    std::vector<int> sts(size_t(3 * nb));
+    // ---- CholeskyQR2 with a certifying downward shift on the first factorisation
+    const double tau_rel = cholqr::certify_shift(M, N);
+    cholqr::pass(h, s, f[0], -tau_rel, true, A, Q1.d());
+    cholqr::pass(h, s, f[1], 0.0, true, Q1.d(), Q);
+    cholqr::factor_product(h, s, f, 2, nullptr, RL);
+    if (read_status(h, stv, 2 * nb, sts.data()) == 0) return {true, cholqr::cert_ratio(tau_rel), false};
+    // ---- shifted CholeskyQR3
+    double* const outs[3] = {Q1.d(), Q2.d(), Q};
+    cholqr::scqr3(h, s, cholqr::robust_shift(M, N), true, f, A, outs);
+    cholqr::factor_product(h, s, f, 3, T.d(), RL);
+    if (read_status(h, stv, 3 * nb, sts.data()) == 0) {
+        cholqr::gram(h, s, T.d(), Q, true);
+        if (max_abs_dev_identity(h, T.d(), N) <= 64.0 * double(N) * cholqr::kU) return {false, 0.0, true};
     }
     // (qc / cq / qr / rq catch this and run the exact Householder emulation on the matrix itself)
     throw Error{XRS_ENUMERIC, "orthogonalize: a numerically rank-deficient matrix above 512 (shifted CholeskyQR3 failed)"};
 }
 
 // ------------------------------------------------------------------------------------------------
-// CholeskyQR2 / shifted CholeskyQR3. Tall: A (m x n) = Q R. Wide: A (m x n) = L Q.
+// CholeskyQR2 / shifted CholeskyQR3. Tall: A (m x n) = Q R. Wide: A (m x n) = L Q. On potrf + trsm; its Grams
+// are plain gemms (cholqr.hpp gram: the known asymmetry).
 OrthResult orthogonalize(xrs_handle_t h, const double* A, size_t m, size_t n, bool wide, double* Q, double* RL) {
-    const size_t N = wide ? m : n;   // Gram size
-    const size_t M = wide ? n : m;   // long dimension
+    const cholqr::Shape s{m, n, wide};
+    const size_t N = s.N(), M = s.M();
     XRS_REQUIRE(N >= 1 && M >= N, "orthogonalize: need a tall (or, wide=true, a wide) matrix");
-    OrthResult res{false, 0.0, false};
     if (N > size_t(kSmallMax)) return orthogonalize_big(h, A, m, n, wide, Q, RL);
-    const int Ni = int(N), nvec = int(M);
     DevBuf G(h, N * N * 8), Dv(h, (N + 32) * 32 * 8), L1(h, N * N * 8), Q1(h, m * n * 8), st(h, 64);
-    auto gram = [&](double* out, const double* X) {
-        if (wide) gemm(h, out, N, N, 1.0, X, n, false, M, X, n, true);   // X X^T
-        else gemm(h, out, N, N, 1.0, X, n, true, M, X, n, false);        // X^T X
-    };
-    auto solve = [&](const double* L, const double* Y, double* X) {
-        trsm(h, wide, L, Dv.d(), Ni, Y, n, X, n, nvec);
-    };
-    // ---- CholeskyQR2 with a certifying downward shift on the first factorisation
-    const double tau_rel = 4.0 * double(M + 2 * N) * kU;
     int* stv = st.as<int>();
-    gram(G.d(), A);
-    potrf(h, G.d(), Ni, -tau_rel, Dv.d(), stv + 0);
-    solve(G.d(), A, Q1.d());
-    gram(L1.d(), Q1.d());
+    // (potrf factors the Grams in place: G, L1 and later L2 hold L1, L2, L3 afterwards)
+    cholqr::Factor f[3] = {{.G = G.d(), .status = stv, .Dinv = Dv.d()}, {.G = L1.d(), .status = stv + 1, .Dinv = Dv.d()}, {}};
+    // ---- CholeskyQR2 with a certifying downward shift on the first factorisation
+    const double tau_rel = cholqr::certify_shift(M, N);
+    const OrthResult certified{true, cholqr::cert_ratio(tau_rel), false};
+    cholqr::pass(h, s, f[0], -tau_rel, false, A, Q1.d());
+    cholqr::gram(h, s, L1.d(), Q1.d(), false);
     {
         // second pass: first-order correction when Q1 is already orthonormal to ~1e-8 (then the
         // neglected O(E^2) term is below u), else a full second Cholesky + TRSM
         DevBuf L2(h, N * N * 8), Li2(h, N * N * 8);
         const unsigned nb = 8;
         double* emax_dev = scratch::dev<double>(h, scratch::kDevOrthEmax, nb);
-        hipLaunchKernelGGL(k_first_order, dim3(nb), dim3(256), 0, h->stream, L1.d(), Ni, L2.d(), Li2.d(), emax_dev);
+        hipLaunchKernelGGL(k_first_order, dim3(nb), dim3(256), 0, h->stream, L1.d(), int(N), L2.d(), Li2.d(), emax_dev);
         check_launch("k_first_order");
         int* hs = scratch::host<int>(h, scratch::kHostResult, 2);
         double* hd = scratch::host<double>(h, scratch::kHostOrthEmax, nb);
@@ -189,53 +149,29 @@ OrthResult orthogonalize(xrs_handle_t h, const double* A, size_t m, size_t n, bo
         double em = 0.0;
         for (unsigned i = 0; i < nb; ++i) em = (hd[i] > em || hd[i] != hd[i]) ? hd[i] : em;
         if (hs[0] == 0 && em <= 1e-8) {
-            if (wide) {
-                gemm(h, Q, N, n, 1.0, Li2.d(), N, false, N, Q1.d(), n, false);      // Q = (I - Elow) Q1
-                gemm(h, RL, N, N, 1.0, G.d(), N, false, N, L2.d(), N, false);      // L = L1 L2
-            } else {
-                gemm(h, Q, m, N, 1.0, Q1.d(), n, false, N, Li2.d(), N, true);      // Q = Q1 (I - Elow)^T
-                gemm(h, RL, N, N, 1.0, L2.d(), N, true, N, G.d(), N, true);        // R = L2^T L1^T
-            }
-            res.certified = true;
-            res.cert_ratio = std::sqrt(0.5 * tau_rel);
-            return res;
+            const cholqr::Factor fo[2] = {f[0], {.L = L2.d(), .Z = Li2.d()}};   // L2 = I + Elow, its inverse I - Elow
+            cholqr::apply_inverse(h, s, fo[1], Q1.d(), Q);
+            cholqr::factor_product(h, s, fo, 2, nullptr, RL);
+            return certified;
         }
     }
-    potrf(h, L1.d(), Ni, 0.0, Dv.d(), stv + 1);
-    solve(L1.d(), Q1.d(), Q);
-    if (wide) gemm(h, RL, N, N, 1.0, G.d(), N, false, N, L1.d(), N, false);   // L = L1 L2
-    else gemm(h, RL, N, N, 1.0, L1.d(), N, true, N, G.d(), N, true);          // R = L2^T L1^T
+    cholqr::factorize(h, N, f[1], 0.0);
+    cholqr::apply_inverse(h, s, f[1], Q1.d(), Q);
+    cholqr::factor_product(h, s, f, 2, nullptr, RL);
     int sts[3] = {0, 0, 0};
-    if (read_status(h, stv, 2, sts) == 0) {
-        res.certified = true;
-        res.cert_ratio = std::sqrt(0.5 * tau_rel);
-        return res;
-    }
+    if (read_status(h, stv, 2, sts) == 0) return certified;
     // ---- shifted CholeskyQR3: valid for any kappa(A) < 1/u
-    res.robust = true;
-    const double s_rel = 11.0 * (double(M) * N + double(N) * (N + 1)) * kU;
+    const OrthResult res{false, 0.0, true};
     DevBuf Q2(h, m * n * 8), L2(h, N * N * 8), T(h, N * N * 8);
-    gram(G.d(), A);
-    potrf(h, G.d(), Ni, s_rel, Dv.d(), stv + 0);
-    solve(G.d(), A, Q1.d());
-    gram(L1.d(), Q1.d());
-    potrf(h, L1.d(), Ni, 0.0, Dv.d(), stv + 1);
-    solve(L1.d(), Q1.d(), Q2.d());
-    gram(L2.d(), Q2.d());
-    potrf(h, L2.d(), Ni, 0.0, Dv.d(), stv + 2);
-    solve(L2.d(), Q2.d(), Q);
-    if (wide) {  // L = L1 L2 L3
-        gemm(h, T.d(), N, N, 1.0, G.d(), N, false, N, L1.d(), N, false);
-        gemm(h, RL, N, N, 1.0, T.d(), N, false, N, L2.d(), N, false);
-    } else {     // R = L3^T L2^T L1^T
-        gemm(h, T.d(), N, N, 1.0, L2.d(), N, true, N, L1.d(), N, true);
-        gemm(h, RL, N, N, 1.0, T.d(), N, false, N, G.d(), N, true);
-    }
+    f[2] = {.G = L2.d(), .status = stv + 2, .Dinv = Dv.d()};
+    double* const outs[3] = {Q1.d(), Q2.d(), Q};
+    cholqr::scqr3(h, s, cholqr::robust_shift(M, N), false, f, A, outs);
+    cholqr::factor_product(h, s, f, 3, T.d(), RL);
     if (read_status(h, stv, 3, sts) == 0) {
         // Cholesky-based passes can "succeed" on an exactly singular Gram with meaningless factors:
         // accept only a verified orthonormal Q (||Q^T Q - I||_max <= 64 n u), else fall through.
-        gram(T.d(), Q);
-        if (max_abs_dev_identity(h, T.d(), N) <= 64.0 * double(N) * kU) return res;
+        cholqr::gram(h, s, T.d(), Q, false);
+        if (max_abs_dev_identity(h, T.d(), N) <= 64.0 * double(N) * cholqr::kU) return res;
     }
     // ---- last resort: unpivoted Householder (exact dgeqrf + dorgqr emulation, one workgroup)
     if (!wide) {
@@ -276,7 +212,7 @@ static size_t qc_core(xrs_handle_t h, const double* A, size_t m, size_t n, doubl
         return exact();
     }
     // certified: sigma_min >= cert*||A||_F > 16 u R_00 (R_00 <= ||A||_F) -> rank n
-    if (o.certified && o.cert_ratio > 64.0 * kDblEps) return n;
+    if (o.certified && o.cert_ratio > 64.0 * cholqr::kEps) return n;
     // not certified: (numerically) rank-deficient or nearly so. A Gram-based factor of such an A is accurate only
     // to ~kappa u in its near-null directions (an entrywise-product TT moved to core 0 measured 5e-12 relative
     // error through the former pivoted QR of the CholeskyQR factor), so the dgeqp3 emulation runs on A itself
@@ -304,7 +240,7 @@ static size_t cq_core(xrs_handle_t h, const double* A, size_t m, size_t n, doubl
         if (e.code != XRS_ENUMERIC) throw;
         return exact();
     }
-    if (o.certified && o.cert_ratio > 64.0 * kDblEps) return m;
+    if (o.certified && o.cert_ratio > 64.0 * cholqr::kEps) return m;
     return exact();   // (see qc)
 }
 

@@ -103,6 +103,7 @@ struct OrthResult {
     bool robust;      // the shifted CholeskyQR3 / Householder path was needed
 };
 
+// CholeskyQR2 with a certifying shift, else shifted CholeskyQR3 (the passes themselves: cholqr.hpp).
 // Tall A (m x n, m >= n): A = Q R, Q m x n orthonormal columns, R n x n upper triangular.
 // Wide B (m x n, m <= n) with wide=true: B = L Q, L m x m lower, Q m x n orthonormal rows.
 OrthResult orthogonalize(xrs_handle_t h, const double* A, size_t m, size_t n, bool wide, double* Q, double* RL);
@@ -115,15 +116,16 @@ void rq(xrs_handle_t h, const double* A, size_t m, size_t n, double* R, double* 
 void svd(xrs_handle_t h, const double* A, size_t m, size_t n, double* U, double* S, double* Vt);
 
 // dense solves (solve.hip): blasWrapper::solve / solve_least_squares semantics; chol_blocked / chol_solve:
-// SPD factorisation of any size (L lower, Z the diagonal-block inverses) and the two triangular sweeps
+// SPD factorisation of any size (chol_full keeping L and Z, the diagonal-block inverses) and the two triangular sweeps
 void solve_dense(xrs_handle_t h, double* X, const double* A, size_t m, size_t n, const double* B, size_t p);
 void svd_solve(xrs_handle_t h, double* X, const double* A, size_t m, size_t n, const double* B, size_t p);
 bool chol_blocked(xrs_handle_t h, const double* A, size_t n, double* L, std::vector<DevBuf>& Z);
 void chol_solve(xrs_handle_t h, const double* L, const std::vector<DevBuf>& Z, size_t n, const double* B, size_t p, double* X);
-// Cholesky of A + shift_rel tr(A) I for any n, enqueued only: status[0 .. chol_full_blocks(n)) (all zero on
-// success), optional L (lower) and Z = L^{-1} (n x n each)
+// The one blocked Cholesky: A + shift_rel tr(A) I for any n, enqueued only: status[0 .. chol_full_blocks(n)) (all
+// zero on success), optional L (lower), Z = L^{-1} (n x n each) and Zdiag, the inverses of the diagonal blocks alone
 int chol_full_blocks(size_t n);
-void chol_full(xrs_handle_t h, const double* A, size_t n, double shift_rel, double* L, double* Z, int* status);
+void chol_full(xrs_handle_t h, const double* A, size_t n, double shift_rel, double* L, double* Z, int* status,
+               std::vector<DevBuf>* Zdiag = nullptr);
 
 // helpers
 void transpose(xrs_handle_t h, double* out, const double* in, size_t rows, size_t cols);

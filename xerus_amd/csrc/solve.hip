@@ -13,13 +13,13 @@
 #include <cstdio>
 #include <vector>
 
+#include "cholqr.hpp"
 #include "reduce_dev.hpp"
 #include "smallla.hpp"
 
 namespace xrs {
 namespace {
 
-constexpr double kEps = 2.220446049250313e-16;
 constexpr int kCholBlock = 256;
 
 // dst (rows x cols, ld ldd) = alpha * src (ld lds)
@@ -55,12 +55,12 @@ __global__ void __launch_bounds__(256) k_sym_flags(const double* __restrict__ A,
                                                    int* __restrict__ flags) {
     double mx = 0.0;
     for (int i = 0; i < nparts; ++i) mx = fmax(mx, part[i]);
-    const double thr = 4.0 * mx * kEps;
+    const double thr = 4.0 * mx * cholqr::kEps;
     bool asym = false, baddiag = false;
     for (size_t e = size_t(blockIdx.x) * 256 + threadIdx.x; e < n * n; e += size_t(gridDim.x) * 256) {
         const size_t i = e / n, j = e - i * n;
         if (j > i && fabs(A[i * n + j] - A[j * n + i]) >= thr) asym = true;
-        if (i == j && (i == 0 ? !(A[0] > 0.0) : A[e] < kEps)) baddiag = true;
+        if (i == j && (i == 0 ? !(A[0] > 0.0) : A[e] < cholqr::kEps)) baddiag = true;
     }
     if (asym) __hip_atomic_fetch_or(&flags[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (baddiag) __hip_atomic_fetch_or(&flags[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -73,43 +73,6 @@ __global__ void k_inv_cut(const double* __restrict__ S, int k, double rcond, dou
 }
 
 }  // namespace
-
-// A = L L^T for symmetric positive definite A (n x n); L lower (n x n, upper part zero), Z the explicit
-// inverses of the diagonal blocks (kCholBlock x kCholBlock each, packed). Returns false if a diagonal
-// block is not positive definite (synchronises once).
-bool chol_blocked(xrs_handle_t h, const double* A, size_t n, double* L, std::vector<DevBuf>& Z) {
-    const size_t nblk = (n + kCholBlock - 1) / kCholBlock;
-    DevBuf W(h, n * n * 8), st(h, nblk * 4), D(h, size_t(kCholBlock) * kCholBlock * 8), Dinv(h, dinv_elems(kCholBlock) * 8);
-    DevBuf P(h, n * kCholBlock * 8), T(h, n * n * 8);
-    XRS_HIP(hipMemcpyAsync(W.d(), A, n * n * 8, hipMemcpyDeviceToDevice, h->stream));
-    XRS_HIP(hipMemsetAsync(L, 0, n * n * 8, h->stream));
-    Z.clear();
-    for (size_t jb = 0; jb < nblk; ++jb) {
-        const size_t j0 = jb * kCholBlock, b = std::min<size_t>(kCholBlock, n - j0), rest = n - j0 - b;
-        copy2d(h, D.d(), b, W.d() + j0 * n + j0, n, b, b);
-        potrf(h, D.d(), int(b), 0.0, Dinv.d(), st.as<int>() + jb);
-        Z.emplace_back(h, b * b * 8);
-        TrinvBatch tb{};
-        tb.L[0] = D.d();
-        tb.Dinv[0] = Dinv.d();
-        tb.X[0] = Z.back().d();
-        tb.n[0] = int(b);
-        trinv_batched(h, tb, 1);
-        copy2d(h, L + j0 * n + j0, n, D.d(), b, b, b);
-        if (!rest) break;
-        // panel L_ij = W_ij Z_jj^T, trailing W -= L_ij L_ij^T
-        gemm(h, P.d(), rest, b, 1.0, W.d() + (j0 + b) * n + j0, n, false, b, Z.back().d(), b, true);
-        copy2d(h, L + (j0 + b) * n + j0, n, P.d(), b, rest, b);
-        gemm_sym(h, T.d(), rest, 1.0, P.d(), b, false, b, P.d(), b, true);
-        const size_t od[2] = {n, n}, id[2] = {rest, rest}, off[2] = {j0 + b, j0 + b};
-        offset_add(h, W.d(), od, T.d(), id, 2, off, -1.0);
-    }
-    std::vector<int> s(nblk);
-    read_status(h, st.as<int>(), int(nblk), s.data());
-    for (int v : s)
-        if (v != 0) return false;
-    return true;
-}
 
 namespace {
 // W[i][i] += rel * trace(W) (one workgroup; the shifted factorisations of the certificates)
@@ -124,10 +87,12 @@ __global__ void __launch_bounds__(256) k_shift_diag(double* __restrict__ W, size
 int chol_full_blocks(size_t n) { return int((n + kCholBlock - 1) / kCholBlock); }
 
 // Cholesky of A + shift_rel tr(A) I of any order, enqueued only: status[b] = potrf status of diagonal
-// block b (chol_full_blocks(n) slots, all zero on success); L (n x n lower, upper zero) and the full
-// inverse Z = L^{-1} (block forward substitution: Z_ii = L_ii^{-1}, Z_ij = -Z_ii L_i,<i Z_<i,j) when
+// block b (chol_full_blocks(n) slots, all zero on success); L (n x n lower, upper zero), the full
+// inverse Z = L^{-1} (block forward substitution: Z_ii = L_ii^{-1}, Z_ij = -Z_ii L_i,<i Z_<i,j) and the
+// inverses of the diagonal blocks alone (appended to Zdiag, each block x block packed: chol_solve's) when
 // the pointers are given. The TT drivers use it for ranks above the batched kernels' 512.
-void chol_full(xrs_handle_t h, const double* A, size_t n, double shift_rel, double* L, double* Z, int* status) {
+void chol_full(xrs_handle_t h, const double* A, size_t n, double shift_rel, double* L, double* Z, int* status,
+               std::vector<DevBuf>* Zdiag) {
     const size_t nblk = size_t(chol_full_blocks(n));
     DevBuf W(h, n * n * 8), Lown(h, L ? 8 : n * n * 8), D(h, size_t(kCholBlock) * kCholBlock * 8),
         Dinv(h, dinv_elems(kCholBlock) * 8), P(h, n * kCholBlock * 8), T(h, n * n * 8);
@@ -139,33 +104,45 @@ void chol_full(xrs_handle_t h, const double* A, size_t n, double shift_rel, doub
     }
     XRS_HIP(hipMemsetAsync(Lm, 0, n * n * 8, h->stream));
     if (Z) XRS_HIP(hipMemsetAsync(Z, 0, n * n * 8, h->stream));
-    DevBuf Zb(h, size_t(kCholBlock) * kCholBlock * 8);
+    DevBuf Zown(h, Zdiag ? 8 : size_t(kCholBlock) * kCholBlock * 8);
     for (size_t jb = 0; jb < nblk; ++jb) {
         const size_t j0 = jb * kCholBlock, b = std::min<size_t>(kCholBlock, n - j0), rest = n - j0 - b;
+        double* Zb = Zdiag ? Zdiag->emplace_back(h, b * b * 8).d() : Zown.d();
         copy2d(h, D.d(), b, W.d() + j0 * n + j0, n, b, b);
         potrf(h, D.d(), int(b), 0.0, Dinv.d(), status + jb);
         TrinvBatch tb{};
         tb.L[0] = D.d();
         tb.Dinv[0] = Dinv.d();
-        tb.X[0] = Zb.d();
+        tb.X[0] = Zb;
         tb.n[0] = int(b);
         trinv_batched(h, tb, 1);
         copy2d(h, Lm + j0 * n + j0, n, D.d(), b, b, b);
         if (Z) {
-            copy2d(h, Z + j0 * n + j0, n, Zb.d(), b, b, b);
+            copy2d(h, Z + j0 * n + j0, n, Zb, b, b, b);
             if (j0) {   // Z[j, :j0] = -Z_jj (L[j, :j0] Z[:j0, :j0])
                 gemm(h, T.d(), b, j0, 1.0, Lm + j0 * n, n, false, j0, Z, n, false);
-                gemm(h, P.d(), b, j0, -1.0, Zb.d(), b, false, b, T.d(), j0, false);
+                gemm(h, P.d(), b, j0, -1.0, Zb, b, false, b, T.d(), j0, false);
                 copy2d(h, Z + j0 * n, n, P.d(), j0, b, j0);
             }
         }
         if (!rest) break;
-        gemm(h, P.d(), rest, b, 1.0, W.d() + (j0 + b) * n + j0, n, false, b, Zb.d(), b, true);   // L_ij = W_ij Z_jj^T
+        gemm(h, P.d(), rest, b, 1.0, W.d() + (j0 + b) * n + j0, n, false, b, Zb, b, true);   // L_ij = W_ij Z_jj^T
         copy2d(h, Lm + (j0 + b) * n + j0, n, P.d(), b, rest, b);
         gemm_sym(h, T.d(), rest, 1.0, P.d(), b, false, b, P.d(), b, true);
         const size_t od[2] = {n, n}, id[2] = {rest, rest}, off[2] = {j0 + b, j0 + b};
         offset_add(h, W.d(), od, T.d(), id, 2, off, -1.0);
     }
+}
+
+// A = L L^T for symmetric positive definite A (n x n): chol_full keeping L (lower, upper part zero) and Z, the
+// inverses of the diagonal blocks. Returns false if a diagonal block is not positive definite (synchronises once).
+bool chol_blocked(xrs_handle_t h, const double* A, size_t n, double* L, std::vector<DevBuf>& Z) {
+    const int nblk = chol_full_blocks(n);
+    DevBuf st(h, size_t(nblk) * 4);
+    Z.clear();
+    chol_full(h, A, n, 0.0, L, nullptr, st.as<int>(), &Z);
+    std::vector<int> s(size_t(nblk), 0);
+    return read_status(h, st.as<int>(), nblk, s.data()) == 0;
 }
 
 // X (n x p) = (L L^T)^{-1} B with the factors of chol_blocked
@@ -218,39 +195,29 @@ __global__ void __launch_bounds__(256) k_pivot_floor(const double* __restrict__ 
 
 static void qr_solve_big(xrs_handle_t h, double* X, const double* A, size_t m, size_t n, const double* B, size_t p, int chol_failed) {
     h->last_solve_path = XRS_SOLVE_QR | chol_failed;
-    const bool wide = m < n;
-    const size_t N = wide ? m : n, M = wide ? n : m;
+    const cholqr::Shape s{m, n, m < n};
+    const size_t N = s.N(), M = s.M();
     const int nb = chol_full_blocks(N);
     DevBuf G(h, N * N * 8), Z1(h, N * N * 8), Z2(h, N * N * 8), Z3(h, N * N * 8), Q1(h, m * n * 8), Q2(h, m * n * 8),
         st(h, size_t(3 * nb + 1) * 4 + 64), Y(h, std::max(M, N) * p * 8), Y2(h, std::max(M, N) * p * 8);
-    XRS_HIP(hipMemsetAsync(st.d(), 0, size_t(3 * nb + 1) * 4, h->stream));   // (last word: k_pivot_floor)
-    auto gram = [&](const double* Xm) {
-        if (wide) gemm_sym(h, G.d(), N, 1.0, Xm, n, false, M, Xm, n, true);   // X X^T
-        else gemm_sym(h, G.d(), N, 1.0, Xm, n, true, M, Xm, n, false);        // X^T X
-    };
-    auto apply = [&](const double* Z, const double* Xm, double* out) {       // tall: X Z^T, wide: Z X
-        if (wide) gemm(h, out, N, n, 1.0, Z, N, false, N, Xm, n, false);
-        else gemm(h, out, m, N, 1.0, Xm, n, false, N, Z, N, true);
-    };
-    const double s_rel = 11.0 * (double(M) * N + double(N) * (N + 1)) * 1.1102230246251565e-16;
-    gram(A);
-    chol_full(h, G.d(), N, s_rel, nullptr, Z1.d(), st.as<int>());
-    apply(Z1.d(), A, Q1.d());
-    gram(Q1.d());
-    chol_full(h, G.d(), N, 0.0, nullptr, Z2.d(), st.as<int>() + nb);
-    hipLaunchKernelGGL(k_pivot_floor, dim3(unsigned((N + 255) / 256)), dim3(256), 0, h->stream, Z2.d(), N,
-                       16.0 * double(M + N) * 1.1102230246251565e-16, st.as<int>() + 3 * nb);
-    check_launch("k_pivot_floor");
-    apply(Z2.d(), Q1.d(), Q2.d());
-    gram(Q2.d());
-    chol_full(h, G.d(), N, 0.0, nullptr, Z3.d(), st.as<int>() + 2 * nb);
-    double* Q = Q1.d();   // (Q1 no longer needed)
-    apply(Z3.d(), Q2.d(), Q);
+    int* stv = st.as<int>();
+    XRS_HIP(hipMemsetAsync(stv, 0, size_t(3 * nb + 1) * 4, h->stream));   // (last word: k_pivot_floor)
+    const cholqr::Factor f[3] = {{.G = G.d(), .status = stv, .Z = Z1.d()},
+                                 {.G = G.d(), .status = stv + nb, .Z = Z2.d()},
+                                 {.G = G.d(), .status = stv + 2 * nb, .Z = Z3.d()}};
+    double* Q = Q1.d();   // (Q1 no longer needed by the third pass)
+    double* const outs[3] = {Q1.d(), Q2.d(), Q};
+    const cholqr::Steps steps{.on_factor = [&](int pass, const cholqr::Factor& f2) {   // (the second one decides, above)
+        if (pass != 1) return;
+        hipLaunchKernelGGL(k_pivot_floor, dim3(unsigned((N + 255) / 256)), dim3(256), 0, h->stream, f2.Z, N,
+                           16.0 * double(M + N) * cholqr::kU, stv + 3 * nb);
+        check_launch("k_pivot_floor");
+    }};
+    cholqr::scqr3(h, s, cholqr::robust_shift(M, N), true, f, A, outs, steps);
     std::vector<int> sts(size_t(3 * nb + 1));
-    read_status(h, st.as<int>(), 3 * nb + 1, sts.data());
-    for (int v : sts)
-        if (v != 0) throw Error{XRS_ENUMERIC, "solve: a numerically rank-deficient system with min(m, n) > 512 is not supported"};
-    if (!wide) {
+    if (read_status(h, stv, 3 * nb + 1, sts.data()) != 0)
+        throw Error{XRS_ENUMERIC, "solve: a numerically rank-deficient system with min(m, n) > 512 is not supported"};
+    if (!s.wide) {
         gemm(h, Y.d(), n, p, 1.0, Q, n, true, m, B, p, false);          // Q^T B
         gemm(h, Y2.d(), n, p, 1.0, Z3.d(), n, true, n, Y.d(), p, false);  // Z3^T
         gemm(h, Y.d(), n, p, 1.0, Z2.d(), n, true, n, Y2.d(), p, false);  // Z2^T
@@ -278,7 +245,7 @@ static void general_solve(xrs_handle_t h, double* X, const double* A, size_t m, 
     h->last_solve_path = XRS_SOLVE_SVD | chol_failed;
     DevBuf U(h, m * k * 8), S(h, k * 8), Vt(h, k * n * 8), Si(h, k * 8), T(h, k * p * 8), R(h, m * p * 8), D(h, n * p * 8);
     svd(h, A, m, n, U.d(), S.d(), Vt.d());
-    hipLaunchKernelGGL(k_inv_cut, dim3(unsigned((k + 255) / 256)), dim3(256), 0, h->stream, S.d(), int(k), 8.0 * kEps, Si.d());
+    hipLaunchKernelGGL(k_inv_cut, dim3(unsigned((k + 255) / 256)), dim3(256), 0, h->stream, S.d(), int(k), 8.0 * cholqr::kEps, Si.d());
     check_launch("k_inv_cut");
     auto apply_pinv = [&](const double* rhs, double* out) {   // out = V S^+ U^T rhs
         gemm(h, T.d(), k, p, 1.0, U.d(), k, true, m, rhs, p, false);

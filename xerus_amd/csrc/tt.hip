@@ -30,6 +30,7 @@
 #include <string>
 #include <vector>
 
+#include "cholqr.hpp"
 #include "reduce_dev.hpp"
 #include "tt_common.hpp"
 
@@ -696,7 +697,7 @@ void rl_sweep(TT& t, const size_t* max_ranks, double eps, double cX, size_t from
         double* L = t.alloc(m * m);
         const OrthResult o = orthogonalize(t.h, t.core[k], m, nn, true, Q, L);
         const double c = o.certified ? cX * o.cert_ratio : 0.0;
-        if (!(m <= nn && c > 16.0 * 2.220446049250313e-16 && eps < 0.5 * c)) {
+        if (!(m <= nn && c > 16.0 * cholqr::kEps && eps < 0.5 * c)) {
             t.release(Q);
             t.release(L);
             for (size_t j = 0; j < k; ++j) orth_right(t, j);

@@ -26,6 +26,7 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "cholqr.hpp"
 #include "reduce_dev.hpp"
 #include "tt_common.hpp"
 
@@ -419,8 +420,6 @@ bool round_truncate(TT& t, const size_t* max_ranks, double eps) {
 // non-orthonormal result) discard the new cores; the caller then runs the reference's sequential sweep.
 namespace {
 
-constexpr double kUnit = 1.1102230246251565e-16;   // 2^-53
-
 // flag = 1 unless 1 / ||W||_F > c ||A||_F, W = R^{-1}, ||A||_F^2 = trG[0] (potrf's trace output)
 __global__ void __launch_bounds__(256) k_rank_cert(const double* __restrict__ W, int n, const double* __restrict__ trG, double c,
                                                    int* __restrict__ flag) {
@@ -505,7 +504,7 @@ __global__ void __launch_bounds__(256) k_rank_cert_gram(const double* __restrict
 
 unsigned grid_for(size_t elems) { return unsigned(std::min<size_t>(std::max<size_t>((elems + 255) / 256, 1), 256)); }
 
-// Shifted CholeskyQR3, enqueued: tall A (m x n, m >= n) = Q R (RL = R, upper, n x n), or wide A (m x n,
+// cholqr.hpp's shifted CholeskyQR3 on the sweep's buffers: tall A (m x n, m >= n) = Q R (RL = R, upper, n x n), or wide A (m x n,
 // m <= n) = L Q (RL = L, lower, m x m). st[0..3) potrf statuses; trG[0] = ||A||_F^2; with Rinv, the
 // explicit inverse of the triangular factor (tall: R^{-1} transposed, i.e. L3^{-1} L2^{-1} L1^{-1} --
 // same Frobenius norm). N = min(m, n) <= 512. pad_kk (tall only): the columns p with p % pad_b >= *pad_kk are
@@ -514,7 +513,8 @@ unsigned grid_for(size_t elems) { return unsigned(std::min<size_t>(std::max<size
 void scqr3(Sweep& sw, const double* A, size_t m, size_t n, bool wide, double* Q, double* RL, int* st, double* trG, double* Rinv,
            const int* pad_kk = nullptr, int pad_b = 1, bool reduce = false, size_t Mg = 0) {
     xrs_handle_t h = sw.t.h;
-    const size_t N = wide ? m : n, M = wide ? n : m;
+    const cholqr::Shape s{m, n, wide};
+    const size_t N = s.N();
     const int Ni = int(N);
     double* G = sw.buf(N * N);
     double* L[3] = {sw.buf(N * N), sw.buf(N * N), sw.buf(N * N)};
@@ -522,34 +522,23 @@ void scqr3(Sweep& sw, const double* A, size_t m, size_t n, bool wide, double* Q,
     double* X1 = sw.buf(m * n);
     double* X2 = sw.buf(m * n);
     double* info = sw.buf(4);
-    const double s_rel = 11.0 * (double(Mg ? Mg : M) * N + double(N) * (N + 1)) * kUnit;
-    const double* cur = A;
-    double* outs[3] = {X1, X2, Q};
-    for (int p = 0; p < 3; ++p) {
-        if (wide) gemm_sym(h, L[p], N, 1.0, cur, n, false, M, cur, n, true);   // X X^T
-        else gemm_sym(h, L[p], N, 1.0, cur, n, true, M, cur, n, false);        // X^T X
-        if (reduce) sw.t.reduce(L[p], N * N);
-        if (pad_kk && !wide) {
-            hipLaunchKernelGGL(k_pad_diag, dim3(1), dim3(256), 0, h->stream, L[p], Ni, pad_b, pad_kk, true);
-            check_launch("k_pad_diag");
-        }
-        potrf(h, L[p], Ni, p == 0 ? s_rel : 0.0, Dv[p], st + p, p == 0 ? info : nullptr);
-        trsm(h, wide, L[p], Dv[p], Ni, cur, n, outs[p], n, int(M));           // tall: X L^{-T}, wide: L^{-1} X
-        cur = outs[p];
-    }
+    auto pad_diag = [&](double* D, bool fill) {
+        hipLaunchKernelGGL(k_pad_diag, dim3(1), dim3(256), 0, h->stream, D, Ni, pad_b, pad_kk, fill);
+        check_launch("k_pad_diag");
+    };
+    // (the Grams are factored in place; only the first pass reports its trace)
+    const cholqr::Factor f[3] = {{.G = L[0], .status = st + 0, .Dinv = Dv[0], .info = info},
+                                 {.G = L[1], .status = st + 1, .Dinv = Dv[1]},
+                                 {.G = L[2], .status = st + 2, .Dinv = Dv[2]}};
+    double* const outs[3] = {X1, X2, Q};
+    const cholqr::Steps steps{.on_gram = [&](double* Gp) {
+        if (reduce) sw.t.reduce(Gp, N * N);
+        if (pad_kk && !wide) pad_diag(Gp, true);
+    }};
+    cholqr::scqr3(h, s, cholqr::robust_shift(Mg ? Mg : s.M(), N), true, f, A, outs, steps);
     if (trG) XRS_HIP(hipMemcpyAsync(trG, info, 8, hipMemcpyDeviceToDevice, h->stream));
-    // RL = L1 L2 L3 (wide) / R = L3^T L2^T L1^T (tall); potrf leaves the upper triangles zero
-    if (wide) {
-        gemm(h, G, N, N, 1.0, L[0], N, false, N, L[1], N, false);
-        gemm(h, RL, N, N, 1.0, G, N, false, N, L[2], N, false);
-    } else {
-        gemm(h, G, N, N, 1.0, L[2], N, true, N, L[1], N, true);
-        gemm(h, RL, N, N, 1.0, G, N, false, N, L[0], N, true);
-        if (pad_kk) {
-            hipLaunchKernelGGL(k_pad_diag, dim3(1), dim3(256), 0, h->stream, RL, Ni, pad_b, pad_kk, false);
-            check_launch("k_pad_diag");
-        }
-    }
+    cholqr::factor_product(h, s, f, 3, G, RL);   // (potrf leaves the upper triangles zero)
+    if (pad_kk && !wide) pad_diag(RL, false);
     if (Rinv) {   // L3^{-1} L2^{-1} L1^{-1} from the identity by three column TRSMs
         double* I0 = sw.buf(N * N);
         double* I1 = sw.buf(N * N);
@@ -565,7 +554,7 @@ void scqr3(Sweep& sw, const double* A, size_t m, size_t n, bool wide, double* Q,
 }  // namespace
 
 // xerus::EPSILON, the default eps of round(maxRanks): an eps above it may cut an edge arbitrarily deep
-constexpr double kDefaultEps = 8 * 2.220446049250313e-16;
+constexpr double kDefaultEps = 8 * cholqr::kEps;
 
 bool round_general(TT& t, const size_t* max_ranks, double eps) {
     const size_t d = t.d;
@@ -607,7 +596,7 @@ bool round_general(TT& t, const size_t* max_ranks, double eps) {
             mmax = std::max(mmax, rr[k] * ng[k]);
             rmax = std::max(rmax, rr[k + 1]);
         }
-        const double s_rel = 11.0 * kUnit * (double(mmax) * double(d) + double(rmax) * double(rmax + 1));
+        const double s_rel = 11.0 * cholqr::kU * (double(mmax) * double(d) + double(rmax) * double(rmax + 1));
         std::vector<double*> A1, A2, A3, G1, Z1, Z2, Z3;
         int cst = 0;
         left_pass(sw, t, t.core, false, A1, st, cst, s_rel, &G1, &Z1);
@@ -629,7 +618,7 @@ bool round_general(TT& t, const size_t* max_ranks, double eps) {
         gemm_grouped(h, j2);
         const int crank = cst;
         for (size_t k = 1; k < d; ++k) {
-            hipLaunchKernelGGL(k_rank_cert_gram, dim3(1), dim3(256), 0, h->stream, W[k], G1[k], int(rr[k]), 32.0 * kUnit, st + cst);
+            hipLaunchKernelGGL(k_rank_cert_gram, dim3(1), dim3(256), 0, h->stream, W[k], G1[k], int(rr[k]), 32.0 * cholqr::kU, st + cst);
             check_launch("k_rank_cert_gram");
             ++cst;
         }
@@ -664,7 +653,7 @@ bool round_general(TT& t, const size_t* max_ranks, double eps) {
         double* trG = sw.buf(1);
         scqr3(sw, A[k], m, b, false, Q, R, st + nst, trG, Rinv, nullptr, 1, sharded, rr[k] * ng[k]);
         nst += 3;
-        hipLaunchKernelGGL(k_rank_cert, dim3(1), dim3(256), 0, h->stream, Rinv, int(b), trG, 32.0 * kUnit, st + nst);
+        hipLaunchKernelGGL(k_rank_cert, dim3(1), dim3(256), 0, h->stream, Rinv, int(b), trG, 32.0 * cholqr::kU, st + nst);
         check_launch("k_rank_cert");
         ++nst;
         const size_t cols = t.n[k + 1] * rr[k + 2];
