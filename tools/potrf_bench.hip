@@ -6,6 +6,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <random>
 #include <vector>
 
@@ -51,17 +52,33 @@ int main(int argc, char** argv) {
     std::vector<long long> st(4096);
     hipMemcpy(st.data(), dstamps, st.size() * 8, hipMemcpyDeviceToHost);
     const int T = (n + 15) / 16;
-    double tA = 0, tB = 0, tC = 0, tD = 0;
-    for (int j = 0; j < T; ++j) {
-        const long long a = st[2 + 4 * j], b = st[3 + 4 * j], c = st[4 + 4 * j];
-        const long long nxt = (j + 1 < T) ? st[2 + 4 * (j + 1)] : st[1];
-        const long long prev = (j == 0) ? st[0] : st[4 + 4 * (j - 1)];
-        tA += a - prev; tB += b - a; tC += c - b; tD += nxt - c;
-        if (j < 3 || j == T - 1)
-            printf("  j=%2d  A(+D prev) %6lld  B %6lld  C %6lld\n", j, a - prev, b - a, c - b);
+    const char* body = getenv("XRS_POTRF_BODY");
+    if (body && strcmp(body, "plain") == 0) {
+        // plain body, wave 0's stamps of step j: 2+4j behind (A), 3+4j behind (B), 4+4j behind (C)
+        double tA = 0, tB = 0, tC = 0;
+        for (int j = 0; j < T; ++j) {
+            const long long a = st[2 + 4 * j], b = st[3 + 4 * j], c = st[4 + 4 * j];
+            const long long prev = (j == 0) ? st[0] : st[4 + 4 * (j - 1)];
+            tA += a - prev; tB += b - a; tC += c - b;
+            if (j < 3 || j == T - 1)
+                printf("  j=%2d  A(+D prev) %6lld  B %6lld  C %6lld\n", j, a - prev, b - a, c - b);
+        }
+        printf("  totals (memtime ticks): A+Dprev %.0f  B %.0f  C %.0f  total %lld\n", tA, tB, tC, st[1] - st[0]);
+    } else {
+        // critical-first body, wave 0's stamps of step j: 2+4j behind barrier X_j, 3+4j behind Y_j (the critical
+        // pair K_j and the panel C_j lie between them), 4+4j behind its factorisation of block j+1; from there to
+        // X_{j+1} it waits for the other waves' trailing update D_j
+        double tK = 0, tB = 0, tW = 0;
+        for (int j = 0; j + 1 < T; ++j) {
+            const long long x = st[2 + 4 * j], y = st[3 + 4 * j], f = st[4 + 4 * j], nxt = st[2 + 4 * (j + 1)];
+            tK += y - x; tB += f - y; tW += nxt - f;
+            if (j < 3 || j % 4 == 3 || j == T - 2)
+                printf("  j=%2d  K_j || C_j %6lld  B_j+1 %6lld  wait for D_j %6lld\n", j, y - x, f - y, nxt - f);
+        }
+        printf("  load + block 0: %lld  last step: %lld  elimination of block 1: %lld of its B\n", st[2] - st[0], st[1] - st[2 + 4 * (T - 1)],
+               T > 1 ? st[1000] - st[3] : 0LL);
+        printf("  totals (memtime ticks): K %.0f  B %.0f  wait %.0f  total %lld\n", tK, tB, tW, st[1] - st[0]);
     }
-    printf("  last block: factor %lld  inverse+rest %lld\n", st[1000] - st[2 + 4 * (T - 1)], st[3 + 4 * (T - 1)] - st[1000]);
-    printf("  totals (memtime ticks): A+Dprev %.0f  B %.0f  C %.0f  total %lld\n", tA, tB, tC, st[1] - st[0]);
     // TRSM (tall: X = A L^{-T})
     for (int it = 0; it < reps + 2; ++it) {
         if (it == 2) hipEventRecord(e0, h->stream);

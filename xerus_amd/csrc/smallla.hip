@@ -18,6 +18,8 @@
 #include "reduce_dev.hpp"
 
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
 
 namespace xrs {
 
@@ -517,27 +519,38 @@ __device__ __forceinline__ void potrf_rr_body(double* __restrict__ G, int n, dou
 }
 
 // ---------------------------------------------------------------------------------------------
-// Lookahead variant of the register-resident Cholesky (n <= 256). Wave 0 factors the diagonal blocks
-// and owns only the tiles of the first column (plus (1,1)), which receive no trailing update after
-// step 0; the other tiles live on waves 1..7 (17 slots each, the plain kernel's register footprint).
-// Step j:
-//   (C_j)  owners of the panel tiles (i, j) form L_ij = G_ij L_jj^{-T} and publish them;
-//   (D1_j) owners of column j+1 apply the rank-16 update of panel j to it; the owner of (j+1, j+1)
-//          publishes it;
-//   (B_{j+1} || D2_j) wave 0 factors block j+1 while waves 1..7 update the rest of the trailing matrix.
-// The diagonal chain (42 % of the plain kernel) thus runs beside the trailing update.
-constexpr int LA_THREADS = PR_THREADS;
-constexpr int LA_WAVES = LA_THREADS / 64;
-constexpr int LA_SLOTS = PR_SLOTS;   // wave 0: tiles 0..16 (column 0 and tile (1,1), final after step 0);
-                                     // waves 1..7: tile 17 + 7 s + (wave - 1)
+// Critical-tiles-first variant of the register-resident Cholesky (n <= 256). Wave 0 factors the diagonal
+// blocks; between "block j factored" and "block j+1 can be factored" only one wave works, the owner of the
+// two tiles (j+1, j) and (j+1, j+1). Everything else of step j runs beside wave 0's factorisation of block
+// j+1. Step j (p = j & 1; Dt / Di are double-buffered, block j in half p):
+//   barrier X_j   L_jj and L_jj^{-1} are in Dt[p] / Di[p]
+//   (K_j || C_j)  wave 1 + j % 7 first takes the critical pair: L_{j+1,j} = G_{j+1,j} L_jj^{-T} -> P[j+1] and
+//          G_{j+1,j+1} -= L_{j+1,j} L_{j+1,j}^T -> Dt[1-p]; every wave forms its other panel tiles (i, j),
+//          i > j+1, and publishes them
+//   barrier Y_j
+//   (B_{j+1} || D_j)  wave 0 factors block j+1 into Dt[1-p] / Di[1-p] while waves 1..7 apply step j to every
+//          trailing tile but (j+1, j+1).
+// The chain pays one critical pair, at most two more panel tiles of its wave and two barriers per step; the
+// trailing update of column j+1 and the other waves' panel tiles are off it. Every tile receives the plain
+// body's MFMA chains in the plain body's order of j: L, Dinv and the status are bit-identical to
+// potrf_rr_body's. Every wave executes 2 T + 2 barriers (T = ceil(n / 16)), on the failure path as well.
+// Ownership (17 slots per wave, the plain kernel's register footprint): wave 0 has (0,0) and (2..15, 0), final
+// after step 0 -- it forms them before it factors block 1 -- and (3,1), (4,1), final
+// after step 1 (two tile updates behind block 1 and two panel tiles in front of block 2 are all the chain pays
+// for the 136 tiles not fitting on seven waves); wave w >= 1 has the critical pairs of steps j = w-1, w+6,
+// w+13 in slots 0..5 (0..3 for w >= 2) and a round-robin share of the other tiles behind them.
+constexpr int CF_THREADS = PR_THREADS;
+constexpr int CF_WAVES = CF_THREADS / 64;
+constexpr int CF_SLOTS = PR_SLOTS;   // 17 (wave 0) + 30 critical + 89 others = 136 tiles
+constexpr int CF_CRIT = 6;           // slots that may hold a critical pair
 
-// slots P, P-1 with kmin <= tk <= kmax: G_ik -= L_ij L_kj^T (interleaved MFMA chains; inactive -> no-op)
+// slots P, P-1 with tk >= kmin and ti >= imin: G_ik -= L_ij L_kj^T (interleaved MFMA chains; inactive -> no-op)
 template <int P>
-__device__ __forceinline__ void la_trail_pair(d4 (&acc)[LA_SLOTS], const int (&ti)[LA_SLOTS], const int (&tk)[LA_SLOTS],
-                                              int kmin, int kmax, const double* Pbuf, int oa) {
-    const bool hi = tk[P] >= kmin && tk[P] <= kmax;
+__device__ __forceinline__ void cf_trail_pair(d4 (&acc)[CF_SLOTS], const int (&ti)[CF_SLOTS], const int (&tk)[CF_SLOTS],
+                                              int kmin, int imin, const double* Pbuf, int oa) {
+    const bool hi = tk[P] >= kmin && ti[P] >= imin;
     bool lo = false;
-    if constexpr (P > 0) lo = tk[P - 1] >= kmin && tk[P - 1] <= kmax;
+    if constexpr (P > 0) lo = tk[P - 1] >= kmin && ti[P - 1] >= imin;
     if (!hi && !lo) return;
     auto op = [&](int tile, int c) -> double {
         return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(Pbuf + max(tile, 0) * PTILE) + oa + 32 * c);
@@ -567,48 +580,74 @@ __device__ __forceinline__ void la_trail_pair(d4 (&acc)[LA_SLOTS], const int (&t
 }
 
 template <int P>
-__device__ __forceinline__ void la_trail_all(d4 (&acc)[LA_SLOTS], const int (&ti)[LA_SLOTS], const int (&tk)[LA_SLOTS],
-                                             int kmin, int kmax, const double* Pbuf, int oa) {
+__device__ __forceinline__ void cf_trail_all(d4 (&acc)[CF_SLOTS], const int (&ti)[CF_SLOTS], const int (&tk)[CF_SLOTS],
+                                             int kmin, int imin, const double* Pbuf, int oa) {
     if constexpr (P >= 0) {
-        la_trail_pair<P>(acc, ti, tk, kmin, kmax, Pbuf, oa);
-        la_trail_all<P - 2>(acc, ti, tk, kmin, kmax, Pbuf, oa);
+        cf_trail_pair<P>(acc, ti, tk, kmin, imin, Pbuf, oa);
+        cf_trail_all<P - 2>(acc, ti, tk, kmin, imin, Pbuf, oa);
     }
 }
 
-__device__ __forceinline__ void potrf_la_body(double* __restrict__ G, int n, double shift_rel, double* __restrict__ Dinv,
+__device__ __forceinline__ void potrf_cf_body(double* __restrict__ G, int n, double shift_rel, double* __restrict__ Dinv,
                                               int* __restrict__ status, double* __restrict__ info,
                                               const double* __restrict__ src = nullptr) {
     const double* __restrict__ S = src != nullptr ? src : G;
-    __shared__ double Dt[PTILE];
-    __shared__ double Di[PTILE];
+    __shared__ double Dt2[2 * PTILE];
+    __shared__ double Di2[2 * PTILE];
     __shared__ double P[PR_TMAX * PTILE];
     __shared__ double ivs[16];
-    __shared__ double red[LA_WAVES];
+    __shared__ double red[CF_WAVES];
     __shared__ int fail;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lr = lane & 15, lg = lane >> 4;
     const int T = (n + 15) >> 4;
-    const int ntiles = T * (T + 1) / 2;
     if (tid == 0) fail = 0;
     PSTAMP(0);
-    block_trace<LA_THREADS>(S, n, red);
-    const double tr = sum_from_zero<LA_WAVES>(red);
+    block_trace<CF_THREADS>(S, n, red);
+    const double tr = sum_from_zero<CF_WAVES>(red);
     if (tid == 0 && info) info[0] = tr;
     const double shift = shift_rel * tr;
 
     // tile ownership + load (identity padding beyond n)
-    int ti[LA_SLOTS], tk[LA_SLOTS];
-    d4 acc[LA_SLOTS];
+    int ti[CF_SLOTS], tk[CF_SLOTS];
+    d4 acc[CF_SLOTS];
+    const int ncrit = wave == 1 ? CF_CRIT : CF_CRIT - 2;
 #pragma unroll
-    for (int s = 0; s < LA_SLOTS; ++s) {
-        const int t = wave == 0 ? s : LA_SLOTS + s * (LA_WAVES - 1) + (wave - 1);
+    for (int s = 0; s < CF_SLOTS; ++s) {
         int i = -1, k = -1;
-        if (t < ntiles) {
-            int start = 0;
-            k = 0;
-            while (t >= start + (T - k)) { start += T - k; ++k; }
-            i = k + (t - start);
+        if (wave == 0) {
+            if (s == 0) {
+                i = 0;
+                k = 0;
+            } else if (s < PR_TMAX - 1) {
+                if (s + 1 < T) {
+                    i = s + 1;
+                    k = 0;
+                }
+            } else if (s - 12 < T) {   // slots 15, 16: (3, 1), (4, 1)
+                i = s - 12;
+                k = 1;
+            }
+        } else if (s < ncrit) {   // the critical pair of step jc: (jc+1, jc) and (jc+1, jc+1)
+            const int jc = wave - 1 + (CF_WAVES - 1) * (s >> 1);
+            if (jc + 1 < T) {
+                i = jc + 1;
+                k = (s & 1) ? jc + 1 : jc;
+            }
+        } else {   // tile rho of the others in column-major order: (i, k), k >= 1, i >= k + 2 (column 1: i >= 5)
+            const int sp = s - ncrit;
+            int rho = sp < 11 ? sp * (CF_WAVES - 1) + wave - 1 : 11 * (CF_WAVES - 1) + (sp - 11) * (CF_WAVES - 2) + wave - 2;
+            int kk = 1, i0 = 5;
+            while (kk < T && rho >= max(T - i0, 0)) {
+                rho -= max(T - i0, 0);
+                ++kk;
+                i0 = kk + 2;
+            }
+            if (kk < T) {
+                k = kk;
+                i = i0 + rho;
+            }
         }
         ti[s] = i;
         tk[s] = k;
@@ -617,14 +656,19 @@ __device__ __forceinline__ void potrf_la_body(double* __restrict__ G, int n, dou
             // lower triangle read: an element above the diagonal (diagonal tiles only) comes from its mirror
             const int er = min(max(16 * i + lg + 4 * q, 0), n - 1), ec = min(max(16 * k + lr, 0), n - 1);
             const int row = max(er, ec), col = min(er, ec);
-            acc[s][q] = S[size_t(row) * n + col];
+            // (32-bit byte offset from the uniform base: half the address registers of the 68 loads in flight)
+            acc[s][q] = *reinterpret_cast<const double*>(reinterpret_cast<const char*>(S) + unsigned(row * n + col) * 8u);
         }
     }
+    // (opaque lane indices: otherwise every load's row and column stay live for the fix-up, and the loaded
+    // tiles spill)
+    int fg = lg, fr = lr;
+    asm volatile("" : "+v"(fg), "+v"(fr));
 #pragma unroll
-    for (int s = 0; s < LA_SLOTS; ++s)
+    for (int s = 0; s < CF_SLOTS; ++s)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const int row = 16 * ti[s] + lg + 4 * q, col = 16 * tk[s] + lr;
+            const int row = 16 * ti[s] + fg + 4 * q, col = 16 * tk[s] + fr;
             const bool inside = ti[s] >= 0 && row < n && col < n;
             const double pad = (row == col) ? 1.0 : 0.0;
             acc[s][q] = inside ? acc[s][q] + ((row == col) ? shift : 0.0) : pad;
@@ -637,68 +681,88 @@ __device__ __forceinline__ void potrf_la_body(double* __restrict__ G, int n, dou
     auto apos = [&](const double* base, int c) -> const double* {   // A/B operand (row lr, k 4c + lg)
         return reinterpret_cast<const double*>(reinterpret_cast<const char*>(base) + oa) + 4 * c;
     };
-    auto publish_diag = [&](int j) {   // owner of (j, j) -> Dt
+    // L_ij = G_ij L_jj^{-T} of slot s (4 MFMAs), published to P[i]
+    auto panel_tile = [&](d4& a, int i, const double* Di) {
+        double* Pi = P + i * PTILE;
 #pragma unroll
-        for (int s = 0; s < LA_SLOTS; ++s)
-            if (ti[s] == j && tk[s] == j) {
+        for (int q = 0; q < 4; ++q) *cpos(Pi, q) = a[q];
+        wave_lds_sync();
+        d4 rr = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-                for (int q = 0; q < 4; ++q) *cpos(Dt, q) = acc[s][q];
-            }
+        for (int c = 0; c < 4; ++c) rr = __builtin_amdgcn_mfma_f64_16x16x4f64(*apos(Pi, c), *apos(Di, c), rr, 0, 0, 0);
+        wave_lds_sync();
+#pragma unroll
+        for (int q = 0; q < 4; ++q) *cpos(Pi, q) = rr[q];
+        a = rr;
     };
-    auto factor_diag = [&](int j) {   // wave 0: Dt -> L_jj (Dt), L_jj^{-1} (Di, Dinv)
-        if (wave == 0) {
-            const int bad = diag_factor16(Dt, Di, ivs, Dinv + size_t(j) * 256, lane, n - 16 * j);
-            if (lane == 0 && bad && fail == 0) fail = 16 * j + bad;
-        }
+    // wave 0: Dt -> L_jj (Dt), L_jj^{-1} (Di, Dinv)
+    auto factor_diag = [&](int j) {
+        double* Dt = Dt2 + (j & 1) * PTILE;
+        double* Di = Di2 + (j & 1) * PTILE;
+        const int bad = diag_factor16(Dt, Di, ivs, Dinv + size_t(j) * 256, lane, n - 16 * j);
+        if (lane == 0 && bad && fail == 0) fail = 16 * j + bad;
     };
-    publish_diag(0);
+    if (wave == 0) {   // owner of (0, 0)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) *cpos(Dt2, q) = acc[0][q];
+    }
     __syncthreads();
-    factor_diag(0);
-    __syncthreads();
+    if (wave == 0) factor_diag(0);
     for (int j = 0; j < T; ++j) {
         // opaque lane offsets per iteration (keeps LICM from hoisting per-slot LDS addresses -> spills)
         asm volatile("" : "+v"(oc), "+v"(oa));
+        double* Dt = Dt2 + (j & 1) * PTILE;
+        double* Di = Di2 + (j & 1) * PTILE;
+        double* Dn = Dt2 + ((j + 1) & 1) * PTILE;
+        __syncthreads();   // X_j
         PSTAMP(2 + 4 * j);
-        // (C_j) panel
+        if (j + 1 < T) {
+            // (K_j) the critical pair
+            if (wave == 1 + j % (CF_WAVES - 1)) {
 #pragma unroll
-        for (int s = 0; s < LA_SLOTS; ++s) {
-            if (tk[s] != j) continue;
+                for (int s = 0; s < CF_CRIT; s += 2) {
+                    if (ti[s] != j + 1 || tk[s] != j || tk[s + 1] != j + 1) continue;
+                    panel_tile(acc[s], j + 1, Di);
+                    wave_lds_sync();
+                    const double* Pi = P + (j + 1) * PTILE;
+                    double b[4];
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) b[c] = *apos(Pi, c);
+#pragma unroll
+                    for (int c = 0; c < 4; ++c)
+                        acc[s + 1] = __builtin_amdgcn_mfma_f64_16x16x4f64(-b[c], b[c], acc[s + 1], 0, 0, 0);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) *cpos(Dn, q) = acc[s + 1][q];
+                }
+            }
+        }
+        // (C_j) the other panel tiles; the diagonal tile's owner takes L_jj back
+#pragma unroll
+        for (int s = 0; s < CF_SLOTS; ++s) {
+            if (tk[s] != j || ti[s] == j + 1) continue;
             if (ti[s] == j) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) acc[s][q] = *cpos(Dt, q);
                 continue;
             }
-            double* Pi = P + ti[s] * PTILE;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) *cpos(Pi, q) = acc[s][q];
-            wave_lds_sync();
-            d4 rr = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int c = 0; c < 4; ++c) rr = __builtin_amdgcn_mfma_f64_16x16x4f64(*apos(Pi, c), *apos(Di, c), rr, 0, 0, 0);
-            wave_lds_sync();
-#pragma unroll
-            for (int q = 0; q < 4; ++q) *cpos(Pi, q) = rr[q];
-            acc[s] = rr;
+            panel_tile(acc[s], ti[s], Di);
         }
-        __syncthreads();
         if (j + 1 >= T) break;
+        __syncthreads();   // Y_j
         PSTAMP(3 + 4 * j);
-        // (D1_j) column j+1 first, then publish the new diagonal block
-        la_trail_all<LA_SLOTS - 1>(acc, ti, tk, j + 1, j + 1, P, oa);
-        publish_diag(j + 1);
-        __syncthreads();
-        PSTAMP(4 + 4 * j);
-        // (B_{j+1} || D2_j); wave 0 factors first, then updates whatever trailing tiles it owns (none
-        // for n = 256 after step 0)
-        if (wave == 0) factor_diag(j + 1);
-        la_trail_all<LA_SLOTS - 1>(acc, ti, tk, j + 2, T - 1, P, oa);
-        __syncthreads();
+        if (wave == 0) {
+            factor_diag(j + 1);   // (B_{j+1})
+            PSTAMP(4 + 4 * j);
+        }
+        // (D_j) every trailing tile but (j+1, j+1); wave 0 has trailing tiles at step 0 only
+        if (wave != 0 || j == 0) cf_trail_all<CF_SLOTS - 1>(acc, ti, tk, j + 1, j + 2, P, oa);
     }
+    __syncthreads();
     PSTAMP(1);
     int sg = lg, sr = lr;
     asm volatile("" : "+v"(sg), "+v"(sr));
 #pragma unroll
-    for (int s = 0; s < LA_SLOTS; ++s) {
+    for (int s = 0; s < CF_SLOTS; ++s) {
         if (ti[s] < 0 || G == nullptr) continue;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -713,19 +777,21 @@ __device__ __forceinline__ void potrf_la_body(double* __restrict__ G, int n, dou
     if (tid == 0) status[0] = fail;
 }
 
-// The lookahead body (n = 256: 150.6 vs 158.8 us per factorisation; n = 100: 64 vs 54 us — one kernel
-// holding both bodies spills, so the lookahead one serves every n <= 256). -DXRS_POTRF_NO_LOOKAHEAD
-// builds the plain body (A/B timing, tools/potrf_bench.hip).
-#ifdef XRS_POTRF_NO_LOOKAHEAD
-#define XRS_POTRF_RR_BODY potrf_rr_body
-#else
-#define XRS_POTRF_RR_BODY potrf_la_body
-#endif
+// Two kernels per entry point: one kernel holding both bodies spills. The critical-first body is the default
+// for every n <= 256 (per factorisation, critical-first / plain: n = 256 136.5 / 149.1 us, 128: 58.0 / 58.7,
+// 100: 50.1 / 49.8, 20: 19.8 / 20.3; tools/potrf_bench.hip); XRS_POTRF_BODY=plain (read at every call;
+// diagnostics and tests) takes the plain right-looking one, whose results are bit-identical.
 #define XRS_POTRF_RR_THREADS PR_THREADS
 __global__ void __launch_bounds__(XRS_POTRF_RR_THREADS) k_potrf_rr(double* __restrict__ G, int n, double shift_rel,
                                                          double* __restrict__ Dinv, int* __restrict__ status,
                                                          double* __restrict__ info) {
-    XRS_POTRF_RR_BODY(G, n, shift_rel, Dinv, status, info);
+    potrf_cf_body(G, n, shift_rel, Dinv, status, info);
+}
+
+__global__ void __launch_bounds__(XRS_POTRF_RR_THREADS) k_potrf_rr_plain(double* __restrict__ G, int n, double shift_rel,
+                                                               double* __restrict__ Dinv, int* __restrict__ status,
+                                                               double* __restrict__ info) {
+    potrf_rr_body(G, n, shift_rel, Dinv, status, info);
 }
 
 // Independent factorisations, one workgroup each (e.g. the Gram matrices of every TT edge).
@@ -736,7 +802,12 @@ __global__ void __launch_bounds__(POT_THREADS) k_potrf32_batched(PotrfBatch b) {
 
 __global__ void __launch_bounds__(XRS_POTRF_RR_THREADS) k_potrf_rr_batched(PotrfBatch b) {
     const int i = blockIdx.x;
-    XRS_POTRF_RR_BODY(b.G[i], b.n[i], b.shift[i], b.Dinv[i], b.status + b.slot[i], nullptr, b.src[i]);
+    potrf_cf_body(b.G[i], b.n[i], b.shift[i], b.Dinv[i], b.status + b.slot[i], nullptr, b.src[i]);
+}
+
+__global__ void __launch_bounds__(XRS_POTRF_RR_THREADS) k_potrf_rr_plain_batched(PotrfBatch b) {
+    const int i = blockIdx.x;
+    potrf_rr_body(b.G[i], b.n[i], b.shift[i], b.Dinv[i], b.status + b.slot[i], nullptr, b.src[i]);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1166,11 +1237,21 @@ __global__ void __launch_bounds__(1024) k_svd_finish(const double* __restrict__ 
 static int dinv_ld(int n) { return n <= PR_TMAX * 16 ? 16 : 32; }
 size_t dinv_elems(int n) { return dinv_ld(n) == 16 ? size_t((n + 15) / 16) * 256 : size_t(n + 32) * 32; }
 
+// XRS_POTRF_BODY=plain (diagnostics and tests: the reference of the critical-first body) takes the plain
+// right-looking kernels for n <= 256; read at every call.
+static bool potrf_plain_body() {
+    const char* e = std::getenv("XRS_POTRF_BODY");
+    return e && std::strcmp(e, "plain") == 0;
+}
+
 void potrf(xrs_handle_t h, double* G, int n, double shift_rel, double* Dinv, int* status_dev, double* info_dev) {
     XRS_REQUIRE(n >= 1 && n <= PMAX, "potrf: n out of range for the single-workgroup kernel");
     KernelTimer timer(h, XRS_KFAM_QR, double(n) * n * n / 3.0, 16.0 * double(n) * n);
     if (dinv_ld(n) == 16) {
-        hipLaunchKernelGGL(k_potrf_rr, dim3(1), dim3(XRS_POTRF_RR_THREADS), 0, h->stream, G, n, shift_rel, Dinv, status_dev, info_dev);
+        if (potrf_plain_body())
+            hipLaunchKernelGGL(k_potrf_rr_plain, dim3(1), dim3(XRS_POTRF_RR_THREADS), 0, h->stream, G, n, shift_rel, Dinv, status_dev, info_dev);
+        else
+            hipLaunchKernelGGL(k_potrf_rr, dim3(1), dim3(XRS_POTRF_RR_THREADS), 0, h->stream, G, n, shift_rel, Dinv, status_dev, info_dev);
         check_launch("k_potrf_rr");
     } else {
         hipLaunchKernelGGL(k_potrf, dim3(1), dim3(POT_THREADS), 0, h->stream, G, n, shift_rel, Dinv, status_dev, info_dev);
@@ -1205,7 +1286,10 @@ void potrf_batched(xrs_handle_t h, const PotrfBatch& b, int count) {
     large.status = b.status;
     if (ns) {
         KernelTimer timer(h, XRS_KFAM_QR, fl_s, 0.0);
-        hipLaunchKernelGGL(k_potrf_rr_batched, dim3(ns), dim3(XRS_POTRF_RR_THREADS), 0, h->stream, small);
+        if (potrf_plain_body())
+            hipLaunchKernelGGL(k_potrf_rr_plain_batched, dim3(ns), dim3(XRS_POTRF_RR_THREADS), 0, h->stream, small);
+        else
+            hipLaunchKernelGGL(k_potrf_rr_batched, dim3(ns), dim3(XRS_POTRF_RR_THREADS), 0, h->stream, small);
         check_launch("k_potrf_rr_batched");
     }
     if (nl) {

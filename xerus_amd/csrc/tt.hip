@@ -240,6 +240,34 @@ void right_gram_step(TT& t, std::vector<double*>& H, double* T, size_t k, bool d
     if (do_reduce) t.reduce(H[k], a * a);
 }
 
+// The step of the two interleaved chains behind which a gated async <x,y> may start (open_dot_gate), or d for
+// "behind the chains" (chain_pass). Step s runs core s on the left chain and core d-1-s on the right one; it
+// is full-size when either has at least a quarter of the largest step's flops. Behind the last full-size step
+// only the boundary cores' steps remain, small GEMMs and reduces that leave the chip nearly idle (rank 256,
+// order 10: 40 us of them and a 13 us gap in front of the batched Cholesky); the product's own first steps
+// are as small, so the gate opens one full-size step earlier still and its first large products meet that
+// idle tail (0.913 against 0.935 ms per step behind the last full-size step and 0.953 behind the chains, DESIGN.md
+// §5), while the product beside all the full-size steps loses (XRS_DOT_GATE=0). XRS_DOT_GATE_EARLY=<e>
+// (diagnostics, read at every pass): 0 keeps the gate behind the chains, e >= 1 opens it behind the e-th
+// full-size step from the end (the earliest one if there are fewer); the default is 2.
+static size_t dot_gate_step(const TT& t) {
+    const size_t d = t.d;
+    int early = 2;
+    if (const char* e = std::getenv("XRS_DOT_GATE_EARLY"); e && e[0] >= '0' && e[0] <= '9' && e[1] == 0) early = e[0] - '0';
+    if (early == 0 || d < 3) return d;
+    auto flops = [&](size_t k) { return double(t.r[k]) * double(t.n[k]) * double(t.r[k + 1]) * double(t.r[k] + t.r[k + 1]); };
+    auto step = [&](size_t s) { return std::max(flops(s), flops(d - 1 - s)); };
+    double top = 0.0;
+    for (size_t s = 0; s + 1 < d; ++s) top = std::max(top, step(s));
+    size_t at = d;
+    for (size_t s = d - 1; s-- > 0;) {
+        if (step(s) * 4.0 < top) continue;
+        at = s;
+        if (--early == 0) break;
+    }
+    return at + 2 == d ? d : at;   // (behind the last step: no thin tail, the gate stays behind the join)
+}
+
 // Both chains (G: left Grams, only with `left`; H: right Grams; `store` owns the memory). Unsharded,
 // concurrently (left on a side stream, right on the main stream) with their launches interleaved step by
 // step. (Both chains' products as one two-entry grid on one stream measured slower: one chain's split-K
@@ -288,12 +316,14 @@ void gram_chains(TT& t, std::vector<double*>& G, std::vector<double*>& H, std::v
         for (size_t k = d - 1; k >= 1; --k) right_gram_step(t, H, TR.d(), k);
         return;
     }
+    const size_t gate_step = dot_gate_step(t);
     StreamFork fork(h);
     for (size_t s = 0; s + 1 < d; ++s) {
         fork.side();
         left_gram_step(t, G, TL.d(), s);
         fork.main();
         right_gram_step(t, H, TR.d(), d - 1 - s);
+        if (s == gate_step) open_dot_gate(h);   // a gated async <x,y> starts beside the chains' thin tail
     }
     fork.join();
 }
